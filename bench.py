@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric: BN254 G1 MSM throughput (Mscalar-mul/s) at 2^26 points.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 26]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 26] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: input generation, W warm-up steps, the K timed steps, the dump of the
+last step's result (--dump-outputs DIR: DIR/g1_msm_affine.npy, float64) and the JSON line with `value` and `ms_per_step`.
+Everything else described below (the full-size linearity check, `roofline`, `cpu_baseline`, `value_incl_scalar_h2d`,
+`secondary`, the N > 1 cross-checks and alternative plan) runs only with --full.
 
 One "step" = one complete G1 multiexp over the whole 2^log_n-point input (bases and scalars already
 resident in HBM): N ranks each run the single-GPU Pippenger on their contiguous point range
@@ -60,6 +65,18 @@ def gen_scalars(n: int, seed: int, device) -> torch.Tensor:
     top = torch.randint(0, R_TOP >> 32, (n, 1), dtype=torch.int64, device=device, generator=g)
     hi = torch.cat([hi, top], dim=1)
     return (lo | (hi << 32)).contiguous()
+
+
+def dump_outputs(path: str, L, result) -> None:
+    """--dump-outputs: the group element the timed step hands its caller, as g1_msm_affine.npy (2, 8): x | y of the affine
+    normalisation of the (12,) u64 Jacobian result (all-zero = infinity), each u64 as its two 32-bit words (low first) in
+    float64, so every value is exact.  (The Jacobian coordinates themselves are not written: the point is the same from run
+    to run, its projective representation is not.)"""
+    os.makedirs(path, exist_ok=True)
+    aff = np.zeros(8, dtype=np.uint64)
+    rc = L.mi355zk_bn254_g1_to_affine(aff.ctypes.data_as(C.c_void_p), np.ascontiguousarray(result, dtype=np.uint64).ctypes.data_as(C.c_void_p))
+    assert rc == 0, rc
+    np.save(os.path.join(path, "g1_msm_affine.npy"), aff.astype("<u8").view("<u4").astype(np.float64).reshape(2, 8))
 
 
 def kernel_sources_sha() -> str:
@@ -669,6 +686,11 @@ def main() -> int:
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary configs (NTT 2^20, G1 / G2 multiexp 2^20, contribute 2^20)")
     ap.add_argument("--secondary-log-n", type=int, default=20)
     ap.add_argument("--no-rows", action="store_true", help="skip the SURVEY 8(f) legs of the secondary block (QAP sums, power_pairs, point ifft, decode)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: per-kernel timings and roofline, the full-size linearity check, the N > 1 "
+                         "cross-checks and alternative plan, the h2d leg, cpu_baseline and the secondary block (each --no-* flag still applies)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's G1 result (affine) to DIR/g1_msm_affine.npy (float64, exact 32-bit words)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -813,10 +835,11 @@ def main() -> int:
     # Inside the timed region only the DOMINANT kernel is bracketed by HIP events (two records per step, on the launch stream): the
     # roofline's `achieved` is measured live over exactly the timed steps.  The other kernel groups are timed in the linearity check's
     # launches below (same shape as a timed step): bracketing all eight groups costs ~20 event records = 0.1-0.2 ms of host time per
-    # step -- nothing at 2^26, 10 % of a 2^20 step.
-    L.mi355zk_prof_reset()
-    L.mi355zk_prof_only(b"msm_accumulate")
-    L.mi355zk_prof_enable(2 if world == 1 else 1)   # (a sharded step is a cell: the check's unsharded launches have another shape, so every group is timed here)
+    # step -- nothing at 2^26, 10 % of a 2^20 step.  (--full only: a plain run times the steps without any event.)
+    if args.full:
+        L.mi355zk_prof_reset()
+        L.mi355zk_prof_only(b"msm_accumulate")
+        L.mi355zk_prof_enable(2 if world == 1 else 1)   # (a sharded step is a cell: the check's unsharded launches have another shape, so every group is timed here)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -829,82 +852,87 @@ def main() -> int:
         if world > 1:
             dist.barrier()
         elapsed = time.perf_counter() - t0
-    L.mi355zk_prof_enable(0)
-    acc_ms_timed, acc_cnt = C.c_double(), C.c_long()
-    L.mi355zk_prof_get(b"msm_accumulate", C.byref(acc_ms_timed), C.byref(acc_cnt))
-    acc_timed = (acc_ms_timed.value / acc_cnt.value) if acc_cnt.value else None
-    if world == 1:
-        L.mi355zk_prof_reset()
-        L.mi355zk_prof_enable(1)   # (the check's launches below carry the per-group timings)
+    if args.full:
+        L.mi355zk_prof_enable(0)
+        acc_ms_timed, acc_cnt = C.c_double(), C.c_long()
+        L.mi355zk_prof_get(b"msm_accumulate", C.byref(acc_ms_timed), C.byref(acc_cnt))
+        acc_timed = (acc_ms_timed.value / acc_cnt.value) if acc_cnt.value else None
+        if world == 1:
+            L.mi355zk_prof_reset()
+            L.mi355zk_prof_enable(1)   # (the check's launches below carry the per-group timings)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, L, result)
 
-    # size-independent check at the FULL size (outside the timed region): linearity in the exponents,
-    #   MSM(bases, s) == MSM(bases, a) + MSM(bases, s - a)   with a uniform, s - a reduced mod r on the device.
-    # (Every launch of the check has the shape of a timed step, so the per-kernel averages of a rocprofv3 trace of
-    # this command are averages over identical launches.)
-    sa = torch.empty_like(scalars)
-    for s in range(shards_local):
-        sa[s * shard:(s + 1) * shard] = gen_scalars(shard, 3_000_017 * (first_shard + s) + 41, dev)
-    sb = scalars.clone()
-    rc = L.mi355zk_bn254_fr_sub_assign_dev(C.c_void_p(sb.data_ptr()), C.c_void_p(sa.data_ptr()), n_local, None)
-    assert rc == 0, rc
-    torch.cuda.synchronize()
-    # (over ALL windows of the local points: the partial over a window group is not linear in the exponents, the carries of
-    # the signed digits cross windows)
-    whole = result if world == 1 else zk.multiexp(worker, (bases, 0), zk.FullDensity(), scalars).wait()
-    sharded_ok = True
-    if world > 1:
-        # the TIMED, sharded `result` itself (window-group partials -> all-gather -> join) against the unsharded evaluation:
-        # one rank of every point range contributes `whole` (all windows of its points), the others the identity
-        contrib = np.ascontiguousarray(whole) if wgroup == 0 else np.zeros(12, dtype=np.uint64)
-        ref_total = zk.shard.allgather_join(contrib, device=dev if backend == "nccl" else None)
-        ra, rb = np.zeros(8, dtype=np.uint64), np.zeros(8, dtype=np.uint64)
-        L.mi355zk_bn254_g1_to_affine(ra.ctypes.data_as(C.c_void_p), np.ascontiguousarray(ref_total).ctypes.data_as(C.c_void_p))
-        L.mi355zk_bn254_g1_to_affine(rb.ctypes.data_as(C.c_void_p), np.ascontiguousarray(result).ctypes.data_as(C.c_void_p))
-        sharded_ok = bool(np.array_equal(ra, rb))
-        assert sharded_ok, "the sharded result differs from the unsharded evaluation"
-    part_a = zk.multiexp(worker, (bases, 0), zk.FullDensity(), sa).wait()
-    part_b = zk.multiexp(worker, (bases, 0), zk.FullDensity(), sb).wait()
-    del sa, sb
-    aff_a, aff_b = np.zeros(8, dtype=np.uint64), np.zeros(8, dtype=np.uint64)
-    L.mi355zk_bn254_g1_to_affine(aff_a.ctypes.data_as(C.c_void_p), np.ascontiguousarray(whole).ctypes.data_as(C.c_void_p))
-    joined = zk.shard.join_partials(np.stack([part_a, part_b]))
-    L.mi355zk_bn254_g1_to_affine(aff_b.ctypes.data_as(C.c_void_p), joined.ctypes.data_as(C.c_void_p))
-    additive_ok = bool(np.array_equal(aff_a, aff_b))
-    assert additive_ok, "full-size linearity check failed"
+    additive_ok = sharded_ok = None
+    if args.full:
+        # size-independent check at the FULL size (outside the timed region): linearity in the exponents,
+        #   MSM(bases, s) == MSM(bases, a) + MSM(bases, s - a)   with a uniform, s - a reduced mod r on the device.
+        # (Every launch of the check has the shape of a timed step, so the per-kernel averages of a rocprofv3 trace of
+        # this command are averages over identical launches.)
+        sa = torch.empty_like(scalars)
+        for s in range(shards_local):
+            sa[s * shard:(s + 1) * shard] = gen_scalars(shard, 3_000_017 * (first_shard + s) + 41, dev)
+        sb = scalars.clone()
+        rc = L.mi355zk_bn254_fr_sub_assign_dev(C.c_void_p(sb.data_ptr()), C.c_void_p(sa.data_ptr()), n_local, None)
+        assert rc == 0, rc
+        torch.cuda.synchronize()
+        # (over ALL windows of the local points: the partial over a window group is not linear in the exponents, the carries of
+        # the signed digits cross windows)
+        whole = result if world == 1 else zk.multiexp(worker, (bases, 0), zk.FullDensity(), scalars).wait()
+        sharded_ok = True
+        if world > 1:
+            # the TIMED, sharded `result` itself (window-group partials -> all-gather -> join) against the unsharded evaluation:
+            # one rank of every point range contributes `whole` (all windows of its points), the others the identity
+            contrib = np.ascontiguousarray(whole) if wgroup == 0 else np.zeros(12, dtype=np.uint64)
+            ref_total = zk.shard.allgather_join(contrib, device=dev if backend == "nccl" else None)
+            ra, rb = np.zeros(8, dtype=np.uint64), np.zeros(8, dtype=np.uint64)
+            L.mi355zk_bn254_g1_to_affine(ra.ctypes.data_as(C.c_void_p), np.ascontiguousarray(ref_total).ctypes.data_as(C.c_void_p))
+            L.mi355zk_bn254_g1_to_affine(rb.ctypes.data_as(C.c_void_p), np.ascontiguousarray(result).ctypes.data_as(C.c_void_p))
+            sharded_ok = bool(np.array_equal(ra, rb))
+            assert sharded_ok, "the sharded result differs from the unsharded evaluation"
+        part_a = zk.multiexp(worker, (bases, 0), zk.FullDensity(), sa).wait()
+        part_b = zk.multiexp(worker, (bases, 0), zk.FullDensity(), sb).wait()
+        del sa, sb
+        aff_a, aff_b = np.zeros(8, dtype=np.uint64), np.zeros(8, dtype=np.uint64)
+        L.mi355zk_bn254_g1_to_affine(aff_a.ctypes.data_as(C.c_void_p), np.ascontiguousarray(whole).ctypes.data_as(C.c_void_p))
+        joined = zk.shard.join_partials(np.stack([part_a, part_b]))
+        L.mi355zk_bn254_g1_to_affine(aff_b.ctypes.data_as(C.c_void_p), joined.ctypes.data_as(C.c_void_p))
+        additive_ok = bool(np.array_equal(aff_a, aff_b))
+        assert additive_ok, "full-size linearity check failed"
 
-    # per-kernel durations measured with HIP events on the launch stream (library hooks): the dominant kernel over the timed steps,
-    # the other groups over the check's launches (identical shapes)
-    L.mi355zk_prof_enable(0)
-    kern = {}
-    for name in ("msm_digits", "msm_sort", "msm_part_scan", "msm_scatter", "msm_bucket", "msm_accumulate_heavy", "msm_accumulate", "msm_reduce"):
-        ms, cnt = C.c_double(), C.c_long()
-        L.mi355zk_prof_get(name.encode(), C.byref(ms), C.byref(cnt))
-        kern[name] = (ms.value / cnt.value) if cnt.value else None
-    if acc_timed is not None:
-        kern["msm_accumulate"] = acc_timed
+        # per-kernel durations measured with HIP events on the launch stream (library hooks): the dominant kernel over the timed steps,
+        # the other groups over the check's launches (identical shapes)
+        L.mi355zk_prof_enable(0)
+        kern = {}
+        for name in ("msm_digits", "msm_sort", "msm_part_scan", "msm_scatter", "msm_bucket", "msm_accumulate_heavy", "msm_accumulate", "msm_reduce"):
+            ms, cnt = C.c_double(), C.c_long()
+            L.mi355zk_prof_get(name.encode(), C.byref(ms), C.byref(cnt))
+            kern[name] = (ms.value / cnt.value) if cnt.value else None
+        if acc_timed is not None:
+            kern["msm_accumulate"] = acc_timed
 
-    # HBM traffic of the dominant kernel comes from a SEPARATE rocprofv3 --pmc pass (counters cannot be read from inside
-    # this process): the committed figure is reported only when it was taken on this workload AND on these kernel sources
-    # (profiles/latest_pmc.json records their hash) -- otherwise null, never a stale number.
-    traffic = None
-    try:
-        with open(os.path.join(ROOT, "profiles", "latest_pmc.json")) as f:
-            pmc = json.load(f)
-        if pmc.get("workload_log_n") == log_n and pmc.get("n_gpus") == world and pmc.get("kernel_sources_sha") == kernel_sources_sha():
-            traffic = pmc["hbm_bytes_per_launch"]
-    except (OSError, ValueError, KeyError):
-        pass
+        # HBM traffic of the dominant kernel comes from a SEPARATE rocprofv3 --pmc pass (counters cannot be read from inside
+        # this process): the committed figure is reported only when it was taken on this workload AND on these kernel sources
+        # (profiles/latest_pmc.json records their hash) -- otherwise null, never a stale number.
+        traffic = None
+        try:
+            with open(os.path.join(ROOT, "profiles", "latest_pmc.json")) as f:
+                pmc = json.load(f)
+            if pmc.get("workload_log_n") == log_n and pmc.get("n_gpus") == world and pmc.get("kernel_sources_sha") == kernel_sources_sha():
+                traffic = pmc["hbm_bytes_per_launch"]
+        except (OSError, ValueError, KeyError):
+            pass
 
     # ---- (N > 1) the OTHER plan in the same run, so that the first real scaling record explains its own efficiency: the default plan gives a
     # rank a (point range x window group) cell (shard.plan: 1 x 2, 1 x 4, 2 x 4); the alternative is point ranges only (N x 1) -- every window
     # reduced once per rank, 1 / N of the points each.  Rank r's N x 1 range is the (r mod window_groups)-th part of the range it already
     # holds, so nothing is generated again.  Same barriers, same max-over-ranks clock, result checked against the timed plan's.
     alt_plan = None
-    if world > 1 and wgroups > 1 and os.environ.get("BENCH_NO_ALT_PLAN") is None:
+    if args.full and world > 1 and wgroups > 1 and os.environ.get("BENCH_NO_ALT_PLAN") is None:
         n_alt = n_total // world
         off = wgroup * n_alt
         b_alt, s_alt = bases[off:off + n_alt], scalars[off:off + n_alt]
@@ -946,7 +974,7 @@ def main() -> int:
     # ---- the same step with the scalars' host-to-device copy inside the timed region (SURVEY 8d defines the metric with "H2D of
     # scalars included"; `value` keeps inputs resident as the bench contract asks): pinned host buffer -> HBM -> multiexp
     h2d = None
-    if not args.no_h2d_leg and world == 1:
+    if args.full and not args.no_h2d_leg and world == 1:
         # the library's host-buffer entry point: the base vector is cached on the device after the first call (the CRS is reused
         # by every proof), the scalars are streamed from (pageable) host memory in chunks overlapped with the kernels
         hb = bases.cpu().numpy().view(np.uint64)
@@ -989,7 +1017,7 @@ def main() -> int:
                        "depending on the host), the better one is value_incl_scalar_h2d; first call = bases + scalars over PCIe"}
         zk.unpin_bases(None)
         del hb, hs, r_first
-    elif not args.no_h2d_leg:
+    elif args.full and not args.no_h2d_leg:
         host_sc = torch.empty(scalars.shape, dtype=scalars.dtype, pin_memory=True)
         host_sc.copy_(scalars)
         stage = torch.empty_like(scalars)
@@ -1016,13 +1044,25 @@ def main() -> int:
         L.mi355zk_bn254_g1_to_affine(aff.ctypes.data_as(C.c_void_p), np.ascontiguousarray(result).ctypes.data_as(C.c_void_p))
         ms_per_step = elapsed / args.steps * 1e3
         value = n_total / (elapsed / args.steps) / 1e6
-        acc_ms = kern["msm_accumulate"]
         nw = C.c_int()
         c_bits = L.mi355zk_msm_window_bits_groups(n_local, wgroups, C.byref(nw))
-        nw_rank = nw.value // wgroups  # windows one launch of this rank accumulates: that share of its scalar-muls' work
-        achieved = BYTES_PER_SCALAR_MUL * (n_local / wgroups) / (acc_ms * 1e-3) / 1e9 if acc_ms else None
-        # integer-ALU model: W mixed adds per scalar-mul, 10 Fq mul each (XYZZ 8M+2S)
-        fq_mul_per_s = (nw_rank * 10 * n_local / (acc_ms * 1e-3)) if acc_ms else None
+        roofline = None
+        if args.full:
+            acc_ms = kern["msm_accumulate"]
+            nw_rank = nw.value // wgroups  # windows one launch of this rank accumulates: that share of its scalar-muls' work
+            achieved = BYTES_PER_SCALAR_MUL * (n_local / wgroups) / (acc_ms * 1e-3) / 1e9 if acc_ms else None
+            # integer-ALU model: W mixed adds per scalar-mul, 10 Fq mul each (XYZZ 8M+2S)
+            fq_mul_per_s = (nw_rank * 10 * n_local / (acc_ms * 1e-3)) if acc_ms else None
+            roofline = {"bound": "hbm", "kernel": "msm_accumulate_kernel", "achieved": round(achieved, 3) if achieved else None,
+                        "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6) if achieved else None,
+                        "traffic": traffic,
+                        "kernel_ms": {k: (round(v, 4) if v is not None else None) for k, v in kern.items()},
+                        "alu_model": {"fq_mul_per_s": fq_mul_per_s,
+                                      "mad_u64_u32_per_s": (nw_rank * MADS_PER_MIXED_ADD * n_local / (acc_ms * 1e-3)) if acc_ms else None,
+                                      "mad_peak_per_s": MAD_PEAK_PER_S,
+                                      "frac": round(nw_rank * MADS_PER_MIXED_ADD * n_local / (acc_ms * 1e-3) / MAD_PEAK_PER_S, 4) if acc_ms else None,
+                                      "note": "W mixed adds (10 Fq products = 1467 v_mad_u64_u32) per scalar-mul in msm_accumulate; "
+                                              "MSM is integer-ALU bound (SURVEY 8d), the multiplier instructions alone are this fraction of the measured v_mad_u64_u32 peak"}}
         out = {
             "metric": "BN254 G1 MSM throughput (Mscalar-mul/s) at 2^%d points" % log_n,
             "value": round(value, 3),
@@ -1043,16 +1083,7 @@ def main() -> int:
                        "bases": "k_i*G, independent k_i" if args.bases == "random" else "tau^i*G (tau-table structure)",
                        "points_per_gpu": n_local, "bases_bytes_per_gpu": n_local * 64, "window_bits": c_bits, "windows": nw.value,
                        "parallelism": "%d point range(s) x %d window group(s), all-gather of 96-B partials" % (pgroups, wgroups)},
-            "roofline": {"bound": "hbm", "kernel": "msm_accumulate_kernel", "achieved": round(achieved, 3) if achieved else None,
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6) if achieved else None,
-                         "traffic": traffic,
-                         "kernel_ms": {k: (round(v, 4) if v is not None else None) for k, v in kern.items()},
-                         "alu_model": {"fq_mul_per_s": fq_mul_per_s,
-                                       "mad_u64_u32_per_s": (nw_rank * MADS_PER_MIXED_ADD * n_local / (acc_ms * 1e-3)) if acc_ms else None,
-                                       "mad_peak_per_s": MAD_PEAK_PER_S,
-                                       "frac": round(nw_rank * MADS_PER_MIXED_ADD * n_local / (acc_ms * 1e-3) / MAD_PEAK_PER_S, 4) if acc_ms else None,
-                                       "note": "W mixed adds (10 Fq products = 1467 v_mad_u64_u32) per scalar-mul in msm_accumulate; "
-                                               "MSM is integer-ALU bound (SURVEY 8d), the multiplier instructions alone are this fraction of the measured v_mad_u64_u32 peak"}},
+            "roofline": roofline,
             "result_affine_x_limb0": hex(int(aff[0])),
             "full_size_linearity_check": additive_ok,
             "sharded_result_matches_unsharded": sharded_ok if world > 1 else None,
@@ -1067,10 +1098,11 @@ def main() -> int:
             "value_incl_scalar_h2d": h2d["value_incl_scalar_h2d"] if h2d else None,
             "incl_scalar_h2d": h2d,
             "input_gen_s": round(t_gen, 2),
+            "full": args.full,   # False: the headline only (roofline, checks, h2d leg, cpu_baseline and secondary are --full)
         }
 
     # ---- CPU baseline: the oracle's restatement of bellman multiexp on the host cores (rank 0, N=1 only)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import oracle_lib as O
 
         ns = 1 << min(args.cpu_sample_log_n, log_n)
@@ -1107,7 +1139,7 @@ def main() -> int:
                                "sample": "first 2^%d points of the same input, oracle restatement of bellman_ce multiexp "
                                          "(c=%d, one thread per window, %d windows), %.2f s" % (int(np.log2(ns)), c_ref, windows, dt),
                                "gpu_matches_oracle_on_sample": ok}
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         del bases, scalars
         torch.cuda.empty_cache()
         out["secondary"] = secondary(zk, L, worker, dev, args.secondary_log_n, cpu=not args.no_cpu_baseline)
@@ -1118,7 +1150,7 @@ def main() -> int:
     # host-buffer call cut into a point range per device (include/mi355zk.h).  A child of rank 0 with a time limit, started AFTER the process group is gone:
     # the other ranks have left by then (their GPUs are idle and their memory is free), so nothing of this optional leg can hang a collective or cost the
     # headline its line.  Needs every GPU visible to rank 0 (nccl runs only).  BENCH_SINGLE_PROCESS_LEG=0 skips it.
-    single_leg = world > 1 and backend == "nccl" and os.environ.get("BENCH_SINGLE_PROCESS_LEG", "1") != "0"
+    single_leg = args.full and world > 1 and backend == "nccl" and os.environ.get("BENCH_SINGLE_PROCESS_LEG", "1") != "0"
     if world > 1:
         if single_leg:
             del bases, scalars

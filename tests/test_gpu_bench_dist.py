@@ -23,7 +23,7 @@ def _free_port():
 
 def _run(n_ranks, bases, log_n=21):
     args = ["bench.py", "--gpus", str(n_ranks), "--steps", "2", "--warmup", "1", "--log-n", str(log_n), "--no-cpu-baseline", "--no-h2d-leg", "--no-secondary",
-            "--bases", bases]
+            "--full", "--bases", bases]
     env = dict(os.environ, BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     if n_ranks == 1:
         cmd = [sys.executable] + args
@@ -66,7 +66,7 @@ def test_eight_ranks_at_the_baseline_size():
 def test_plain_command_launches_its_own_ranks():
     """`python3 bench.py --gpus 4 ...` exactly as typed (no torchrun, WORLD_SIZE unset): bench.py starts the ranks itself and rank 0
     prints the one JSON line -- so the first multi-GPU lease produces a scaling curve instead of an argument error."""
-    args = [sys.executable, "bench.py", "--gpus", "4", "--steps", "2", "--warmup", "1", "--log-n", "21", "--no-cpu-baseline", "--no-h2d-leg", "--no-secondary"]
+    args = [sys.executable, "bench.py", "--gpus", "4", "--steps", "2", "--warmup", "1", "--log-n", "21", "--no-cpu-baseline", "--no-h2d-leg", "--no-secondary", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run(args, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
@@ -89,10 +89,34 @@ def test_plain_command_launches_its_own_ranks():
 def test_single_process_multi_gpu_leg_of_the_bench():
     """When bench.py's process sees several GPUs its secondary block also times the single-process multi-GPU mode of the C ABI
     (mi355zk_init with n > 1); BENCH_MULTI_LOGICAL=4 exercises that leg with four logical devices on the one GPU there is: same point."""
-    args = [sys.executable, "bench.py", "--log-n", "20", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-h2d-leg"]
+    args = [sys.executable, "bench.py", "--log-n", "20", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-h2d-leg", "--full"]
     env = dict(os.environ, BENCH_MULTI_LOGICAL="4")
     out = subprocess.run(args, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     got = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     leg = got["secondary"]["single_process_multi_gpu_2e24"]
     assert [len(r["devices"]) for r in leg["runs"]] == [1, 2, 4] and all(r["same_point_as_device_resident_call"] for r in leg["runs"])
+
+
+def test_plain_run_reports_the_headline_and_dumps_the_last_step(tmp_path):
+    """`bench.py` without --full: the timed steps and the headline only (no roofline, checks or extra legs); --dump-outputs DIR writes
+    the last step's result (affine) as exact 32-bit words in float64, and two runs with the same arguments write the same array."""
+    import numpy as np
+
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        args = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--log-n", "20", "--dump-outputs", str(d)]
+        out = subprocess.run(args, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        got = json.loads(lines[0])
+        assert got["full"] is False and got["steps"] == 3 and got["ms_per_step"] > 0 and got["value"] > 0
+        assert got["roofline"] is None and got["full_size_linearity_check"] is None and got["incl_scalar_h2d"] is None
+        assert "cpu_baseline" not in got and "secondary" not in got
+        aff = np.load(d / "g1_msm_affine.npy")
+        assert aff.dtype == np.float64 and aff.shape == (2, 8) and bool(np.all(aff == np.floor(aff))) and float(aff.max()) < 2.0 ** 32
+        assert hex(int(aff[0, 0]) | (int(aff[0, 1]) << 32)) == got["result_affine_x_limb0"]
+        dumps.append(aff)
+    assert np.array_equal(dumps[0], dumps[1])

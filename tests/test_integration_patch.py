@@ -2,9 +2,12 @@
   - integration/mi355zk.rs's `extern "C"` block is the one tools/gen_rust_ffi.py derives from include/mi355zk.h, and -- parsed back
     independently -- every item has the name, the argument count and the pointer / integer shape of its C prototype;
   - the symbols the hand-written shim code calls exist in that block;
-  - integration/bellman_mi355zk.patch carries exactly that file as bellman/src/mi355zk.rs and applies (`patch --dry-run -p1`) to a copy
-    of the reference's bellman/ tree (multiexp.rs:330-355, source.rs:21-34,72-118, domain.rs:263-272).  That last check needs
-    /root/reference and is skipped where it is absent (the GPU box)."""
+  - integration/bellman_mi355zk.patch carries exactly that file as bellman/src/mi355zk.rs and applies (`patch --dry-run -p1`) to the
+    reference's bellman/ tree (multiexp.rs:330-355, source.rs:21-34,72-118, domain.rs:263-272): every hunk's pre-image is the text the
+    reference holds at that place (sha256 digests taken from the reference tree: tests/golden/bellman_patch_preimage.json, written by
+    tests/golden/gen_bellman_preimage.py), and the patch applies to files rebuilt from those pre-images."""
+import hashlib
+import json
 import os
 import re
 import shutil
@@ -19,7 +22,7 @@ import gen_rust_ffi as gen  # noqa: E402
 
 RS = os.path.join(ROOT, "integration", "mi355zk.rs")
 PATCH = os.path.join(ROOT, "integration", "bellman_mi355zk.patch")
-REF_BELLMAN = "/root/reference/bellman"
+PREIMAGE = os.path.join(ROOT, "tests", "golden", "bellman_patch_preimage.json")
 
 
 def _rust_items():
@@ -79,10 +82,57 @@ def test_the_patch_carries_this_file():
     assert "try_multiexp::<Q, D, G, S>" in patch and "try_best_fft::<E, T>" in patch
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_BELLMAN) or shutil.which("patch") is None, reason="needs /root/reference/bellman and patch(1)")
+def _preimages():
+    """{relative path: [(first line, [pre-image lines]), ...]} of the patch's hunks (context and removed lines), from the patch itself"""
+    hunks, cur, lines = {}, None, iter(open(PATCH).read().splitlines())
+    for ln in lines:
+        if ln.startswith("--- a/"):
+            cur = ln[len("--- a/"):].split("\t")[0]
+        m = re.match(r"@@ -(\d+)(?:,(\d+))? \+\d+(?:,(\d+))? @@", ln)
+        if not m:
+            continue
+        old, new, pre = int(m.group(2) or 1), int(m.group(3) or 1), []
+        while old or new:
+            body = next(lines)
+            if body.startswith("\\"):
+                continue
+            tag, text = body[:1], body[1:]
+            if tag in (" ", "-"):
+                pre.append(text)
+                old -= 1
+            if tag in (" ", "+"):
+                new -= 1
+        if pre:
+            hunks.setdefault(cur, []).append((int(m.group(1)), pre))
+    return hunks
+
+
+def _digest(lines):
+    """as tests/golden/gen_bellman_preimage.py takes it from the reference tree"""
+    return hashlib.sha256("".join(ln + "\n" for ln in lines).encode()).hexdigest()
+
+
+def test_the_patch_preimage_is_the_reference_text():
+    """Each hunk replaces or keeps exactly the lines the reference's bellman/ holds at its line range, so `patch` applies it in place, no fuzz."""
+    want = json.load(open(PREIMAGE))["files"]
+    got = _preimages()
+    assert sorted(got) == sorted(want)
+    for rel, hunks in got.items():
+        assert [[first, len(pre), _digest(pre)] for first, pre in hunks] == want[rel]["hunks"], rel
+
+
+@pytest.mark.skipif(shutil.which("patch") is None, reason="needs patch(1)")
 def test_the_patch_applies_to_the_reference_tree(tmp_path):
+    # the reference's files as far as the patch reads them: every hunk's pre-image at its line (the digests above tie it to the reference
+    # text), a placeholder on every other line, each file its reference length
     work = tmp_path / "bellman"
-    shutil.copytree(REF_BELLMAN, work)
+    want = json.load(open(PREIMAGE))["files"]
+    for rel, hunks in _preimages().items():
+        lines = ["// reference line %d (not stored)" % (i + 1) for i in range(want[rel]["lines"])]
+        for first, pre in hunks:
+            lines[first - 1:first - 1 + len(pre)] = pre
+        (work / rel).parent.mkdir(parents=True, exist_ok=True)
+        (work / rel).write_text("".join(ln + "\n" for ln in lines))
     r = subprocess.run(["patch", "--dry-run", "-p1", "-i", PATCH], cwd=work, capture_output=True, text=True)
     assert r.returncode == 0 and "FAILED" not in r.stdout and "fuzz" not in r.stdout, r.stdout + r.stderr
     r = subprocess.run(["patch", "-p1", "-i", PATCH], cwd=work, capture_output=True, text=True)

@@ -10,6 +10,6 @@ for round in 1 2 3; do
     for ln in 20 24; do
       echo "$tag ntt 2^$ln  $(MI355ZK_SO=$so python tools/bench_ntt.py --log-n $ln --iters 40 --check | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print({k:(v["ms"] if isinstance(v,dict) else v) for k,v in d.items()})')"
     done
-    echo "$tag msm 2^26 $(MI355ZK_SO=$so python bench.py --steps 5 --warmup 2 --no-secondary --no-h2d-leg --cpu-sample-log-n 16 | python -c 'import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d["ms_per_step"], d["roofline"]["kernel_ms"]["msm_accumulate"], d["full_size_linearity_check"], d["cpu_baseline"]["gpu_matches_oracle_on_sample"], d["result_affine_x_limb0"])')"
+    echo "$tag msm 2^26 $(MI355ZK_SO=$so python bench.py --steps 5 --warmup 2 --no-secondary --no-h2d-leg --full --cpu-sample-log-n 16 | python -c 'import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d["ms_per_step"], d["roofline"]["kernel_ms"]["msm_accumulate"], d["full_size_linearity_check"], d["cpu_baseline"]["gpu_matches_oracle_on_sample"], d["result_affine_x_limb0"])')"
   done
 done

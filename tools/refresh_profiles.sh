@@ -6,7 +6,7 @@ R=/root/repo
 O=$R/gpurun_out/refresh
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py"
+B="python $R/bench.py --full"
 timeout 400 $B > $O/bench_n1.json 2> $O/bench_n1.err
 timeout 200 $B --log-n 20 --steps 20 --warmup 3 --no-secondary > $O/bench_2e20.json 2>/dev/null
 timeout 400 rocprofv3 --kernel-trace -d /tmp/p_kt -- $B --steps 3 --warmup 1 --no-cpu-baseline --no-h2d-leg --no-secondary > $O/kt.log 2>&1

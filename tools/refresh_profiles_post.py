@@ -16,7 +16,7 @@ put("contribute_2e20.json", "contribute_2e20.json"); put("host_entry.json", "hos
 put("ntt_16_20_24.json", "ntt_16_20_24.json"); put("skew_2e26.json", "skew_2e26.json"); put("bench_n1_tau.json", "bench_n1_tau.json")
 put("table_mode.json", "table_mode.json"); put("ubench_valu.txt", "ubench_valu.txt"); put("ntt_other_sizes.json", "ntt_other_sizes.json"); put("ubench_fieldmul.txt", "ubench_fieldmul.txt"); put("ubench_wave_bucket.txt", "ubench_wave_bucket.txt"); put("prover.json", "prover.json"); put("skew_small.json", "skew_16_20.json")
 put("msm26_kernel_stats.txt", "msm26_kernel_stats.txt",
-    "# rocprofv3 --kernel-trace -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline   (MI355X, 2^26-point G1 MSM)\n"
+    "# rocprofv3 --kernel-trace -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline   (MI355X, 2^26-point G1 MSM)\n"
     "# summarised from the rocpd database with tools/rocpd_summary.py (ROCm 7.2 rocprofv3 writes rocpd; same numbers as --stats)\n"
     "# batch_exp_kernel = synthetic-input generation (outside the timed region); every msm_* launch is a full-size step\n"
     "# (1 warm-up + 3 timed + 2 of the linearity check); msm_accumulate_kernel is the dominant kernel of a step\n")
@@ -25,7 +25,7 @@ put("msm20_timeline.txt", "msm20_timeline.txt", "# rocprofv3 --kernel-trace -- p
 put("ntt20_kernel_stats.txt", "ntt20_kernel_stats.txt", "# rocprofv3 --kernel-trace -- python tools/bench_ntt.py --check   (MI355X, 2^20 Fr NTT, 20 iterations x 4 ops)\n")
 put("msm26_accumulate_sq_pmc.txt", "msm26_accumulate_sq_pmc.txt", "# rocprofv3 --pmc SQ_* (one pass, 8 counters) on msm_accumulate_kernel<Fq>, 2^26 points, MI355X\n")
 with open(os.path.join(DST, f"{tag}_msm26_pmc_hbm.txt"), "w") as f:
-    f.write("# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline  (MI355X)\n"
+    f.write("# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline  (MI355X)\n"
             "# unit: KB per dispatch.  gfx950 FETCH_SIZE tallies 64 B per L2->fabric request: coalesced 16 B/lane streams (128-byte requests)\n"
             "# read half their bytes (msm_digits_hist_kernel: 2 GiB of scalars -> 1.05e6 KB), random 64-byte records and 16-byte words read\n"
             "# exactly 64 B per access (profiles/r02_ubench_gather_fetch_calibration.txt).  msm_accumulate_kernel is gathers only: no x2.\n")
@@ -101,12 +101,12 @@ rows = []
 b = J("bench_n1.json")
 if b:
     k = b["roofline"]["kernel_ms"]; sec = b.get("secondary", {}); h = b.get("incl_scalar_h2d") or {}
-    rows.append((f"`{tag}_bench_n1.json`", "`python bench.py`", f"2^26 G1 MSM: `value` **{b['value']:.0f} Mscalar-mul/s** ({b['ms_per_step']:.2f} ms; HIP events: accumulate {k['msm_accumulate']:.2f}, digits {k['msm_digits']:.2f}, partition {k['msm_sort']:.2f}, reduce {k['msm_reduce']:.2f} ms); `value_incl_scalar_h2d` **{b['value_incl_scalar_h2d']:.0f}** ({h.get('ms_per_step')} ms; pageable {h.get('pageable_exponents_ms')}, page-locked {h.get('page_locked_exponents_ms')}, first call {h.get('first_call_incl_bases_h2d_ms')}); roofline frac {b['roofline']['frac']}; CPU: {b['cpu_baseline']['value']} M/s on {b['cpu_baseline']['cores']} threads"))
+    rows.append((f"`{tag}_bench_n1.json`", "`python bench.py --full`", f"2^26 G1 MSM: `value` **{b['value']:.0f} Mscalar-mul/s** ({b['ms_per_step']:.2f} ms; HIP events: accumulate {k['msm_accumulate']:.2f}, digits {k['msm_digits']:.2f}, partition {k['msm_sort']:.2f}, reduce {k['msm_reduce']:.2f} ms); `value_incl_scalar_h2d` **{b['value_incl_scalar_h2d']:.0f}** ({h.get('ms_per_step')} ms; pageable {h.get('pageable_exponents_ms')}, page-locked {h.get('page_locked_exponents_ms')}, first call {h.get('first_call_incl_bases_h2d_ms')}); roofline frac {b['roofline']['frac']}; CPU: {b['cpu_baseline']['value']} M/s on {b['cpu_baseline']['cores']} threads"))
     n = sec.get("fr_ntt_2e20"); g1 = sec.get("g1_msm_2e20"); g2 = sec.get("g2_msm_2e20"); c = sec.get("contribute_2e20")
     if n and g1 and g2 and c:
         rows.append(("  `secondary`", "same run", f"2^20 Fr NTT fft / ifft / coset_fft {n['fft']['ms']} / {n['ifft']['ms']} / {n['coset_fft']['ms']} ms (pass {n['roofline']['pass_ms']} ms = {n['roofline']['achieved']} GB/s algorithmic); 2^20 G1 multiexp {g1['ms']} ms = {g1['value']} M/s (table mode {g1['table_mode']['ms']} ms = {g1['table_mode']['value']}); 2^20 G2 {g2['ms']} ms = {g2['value']} M/s (table mode {g2['table_mode']['ms']} = {g2['table_mode']['value']}); contribute 2^20 {c['ms']} ms = {c['value']} Mpoint/s"))
 b20 = J("bench_2e20.json")
-if b20: rows.append((f"`{tag}_bench_2e20.json`, `{tag}_msm20_timeline.txt`, `{tag}_msm16_timeline.txt`", "`bench.py --log-n 20 --no-secondary`; `rocprofv3 --kernel-trace -- tools/trace_one_msm.py`", f"BASELINE config 2: {b20['ms_per_step']} ms = {b20['value']:.0f} M/s (kernels: {b20['roofline']['kernel_ms']}); launch-by-launch timelines of one 2^20 and one 2^16 call"))
+if b20: rows.append((f"`{tag}_bench_2e20.json`, `{tag}_msm20_timeline.txt`, `{tag}_msm16_timeline.txt`", "`bench.py --full --log-n 20 --no-secondary`; `rocprofv3 --kernel-trace -- tools/trace_one_msm.py`", f"BASELINE config 2: {b20['ms_per_step']} ms = {b20['value']:.0f} M/s (kernels: {b20['roofline']['kernel_ms']}); launch-by-launch timelines of one 2^20 and one 2^16 call"))
 acc = stat("zk::msm_accumulate_kernel<Fq>")
 if acc: rows.append((f"`{tag}_msm26_kernel_stats.txt`, `{tag}_msm26_pmc_hbm.txt`, `{tag}_msm26_accumulate_sq_pmc.txt`, `latest_pmc.json`", "`rocprofv3 --kernel-trace` / `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` / `--pmc SQ_*` (separate passes) `-- python bench.py ...`", f"`msm_accumulate_kernel<Fq>` avg **{acc / 1e3:.2f} ms** per launch; HBM traffic {(fetch + write) * 1024 / 1e9:.1f} GB per launch = {(fetch + write) * 1024 / (96 * 2**26):.1f} x the algorithmic 6.44 GB (FETCH {fetch * 1024 / 1e9:.1f} + WRITE {write * 1024 / 1e9:.1f})"))
 nt = J("ntt_16_20_24.json")
@@ -129,7 +129,7 @@ for name, cmd, what in (("ab_quad.txt", "`tools/ab_quad.sh`", "quad additions in
                         ("skew_2e26.json", "`tools/bench_skew.py --log-n 26`", "prover-like exponents at 2^26"), ("skew_16_20.json", "`tools/bench_skew.py`", "prover-like exponents at 2^16 / 2^20"),
                         ("ubench_valu.txt", "`tools/bin/ubench_valu`", "issue cost of the VALU instructions the kernels are made of"),
                         ("ubench_fieldmul.txt", "`tools/bin/ubench_fieldmul`", "field product rates"), ("ubench_wave_bucket.txt", "`tools/bin/ubench_wave_bucket`", "lane per bucket vs wave per bucket"),
-                        ("bench_n1_tau.json", "`python bench.py --bases tau`", "the headline on tau-table bases")):
+                        ("bench_n1_tau.json", "`python bench.py --full --bases tau`", "the headline on tau-table bases")):
     if os.path.exists(os.path.join(DST, f"{tag}_{name}")): rows.append((f"`{tag}_{name}`", cmd, what))
 hand = [("`r04_exp_cu_mask.txt`", "`tools/exp_cu_mask.py`", "CU-masked side stream beside the accumulation: measured, rejected (DESIGN 6)"),
         ("`r04_small_n_sweep.txt`", "`tools/sweep_small_n.sh`", "every window width at 2^10 .. 2^20 and the reduce schedule after the quad additions: the measured table did not move"),

@@ -1,6 +1,6 @@
 # re-measure the short-call window table (choose_geom) and the reduce schedule after the quad additions (round 4)
 # usage on the GPU box: bash tools/sweep_small_n.sh > gpurun_out/r04/small_n_sweep.txt
-run() { python bench.py --log-n $1 --steps 30 --warmup 10 --no-secondary --no-cpu-baseline --no-h2d-leg 2>/dev/null | python -c "import sys,json; d=json.load(sys.stdin); k=d['roofline']['kernel_ms']; print(d['ms_per_step'], 'ms  W', d['config']['windows'], 'bits', d['config']['window_bits'], 'reduce', k['msm_reduce'], 'acc', k['msm_accumulate'])"; }
+run() { python bench.py --log-n $1 --steps 30 --warmup 10 --no-secondary --no-cpu-baseline --no-h2d-leg --full 2>/dev/null | python -c "import sys,json; d=json.load(sys.stdin); k=d['roofline']['kernel_ms']; print(d['ms_per_step'], 'ms  W', d['config']['windows'], 'bits', d['config']['window_bits'], 'reduce', k['msm_reduce'], 'acc', k['msm_accumulate'])"; }
 echo "# G1, uniform exponents: ms per call by forced window width c (MI355ZK_MSM_C); 'default' = the table in choose_geom"
 for ln in 10 12 13 14 15 16 17 18 19 20; do
   echo -n "2^$ln default: "; run $ln
