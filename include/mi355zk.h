@@ -16,8 +16,11 @@
  *                       (the element type of multiexp's `exponents`, multiexp.rs:334).
  *   G1 affine base    = 64 bytes  x || y            (RawEncodable layout, ec.rs:653-664)
  *   G2 affine base    = 128 bytes x.c0 || x.c1 || y.c0 || y.c1
- *                       the ALL-ZERO record is the point at infinity (ec.rs:673-675); the shim must
- *                       zero the record itself when `is_zero()` (the reference's raw encoder does not).
+ *                       the ALL-ZERO record is the point at infinity (ec.rs:673-675).  The caller's own
+ *                       records -- `G1Affine { x, y, infinity: bool }`, 72 B; G2Affine, 136 B (ec.rs:14-18),
+ *                       whose identity is x = 0, y = R, infinity = true -- go to the STRIDED entry points
+ *                       (mi355zk_bn254_g{1,2}_msm_strided, mi355zk_bases_cache_pin_strided) as they lie in
+ *                       memory: the library repacks them on the device.  That is the path the Rust shim takes.
  *   Jacobian result   = X || Y || Z (12 / 24 u64), Z == 0 <=> infinity (ec.rs:227-246).  Any
  *                       representative of the group element may be returned (projective equality is
  *                       by value, ec.rs:45-85).
@@ -91,8 +94,9 @@ const char *mi355zk_version(void);
 /* The ABI revision this library was built with; a binding compares it with the MI355ZK_ABI_VERSION of the header it was written against
  * and refuses to run on a mismatch (lib.py and integration/mi355zk.rs do).  Bumped whenever a prototype or the meaning of an argument
  * changes: 6 = round 5's breaks -- batch_exp's `same_scalar` and point_fft's `inverse` became the bit masks `mode` (a legacy "true" of 2
- * would now read as MI355ZK_G2_TRUSTED_SUBGROUP), sparse_matvec[_dev] gained a trailing `flags`. */
-#define MI355ZK_ABI_VERSION 6
+ * would now read as MI355ZK_G2_TRUSTED_SUBGROUP), sparse_matvec[_dev] gained a trailing `flags`; 7 = the strided record entry points
+ * (mi355zk_bn254_g{1,2}_msm_strided, mi355zk_bases_cache_pin_strided, mi355zk_bn254_g{1,2}_records_pack_dev). */
+#define MI355ZK_ABI_VERSION 7
 int mi355zk_abi_version(void);
 
 /* ---- multiexp: host buffers.  Replaces bellman/src/multiexp.rs:330 `multiexp` for
@@ -102,8 +106,8 @@ int mi355zk_bn254_g1_msm(const uint8_t *bases, size_t n_bases, size_t base_offse
                          const uint32_t *density, size_t density_bits,
                          uint64_t out_xyz[12]);
 /* The CRS is an immutable `Arc<Vec<G>>` reused by every proof (groth16/mod.rs:216-238).  A caller that can PROMISE that --
- * the Rust shim keeps a clone of the Arc next to its raw-record vector, so the allocation is neither rewritten nor freed --
- * pins the vector: mi355zk_bases_cache_pin(ptr, n_bases, group 1|2).  Host-buffer calls over exactly (ptr, n_bases) then keep
+ * the Rust shim keeps a clone of the Arc in a registry, so the allocation is neither rewritten nor freed, and pins the `Vec<G>` itself
+ * with mi355zk_bases_cache_pin_strided (below) -- pins the vector: mi355zk_bases_cache_pin(ptr, n_bases, group 1|2).  Host-buffer calls over exactly (ptr, n_bases) then keep
  * their uploaded copy on the device and only the scalars cross PCIe after the first call (large calls are streamed: chunked
  * upload overlapped with the kernels).  Vectors that were NOT pinned are uploaded on every call: the plain `const uint8_t*`
  * entry is correct whatever the caller does with its buffer between calls.  mi355zk_bases_cache_invalidate(ptr) ends the
@@ -125,6 +129,43 @@ int mi355zk_bn254_g2_msm(const uint8_t *bases, size_t n_bases, size_t base_offse
                          const uint64_t *scalars, size_t n_scalars,
                          const uint32_t *density, size_t density_bits,
                          uint64_t out_xyz[24]);
+
+/* ---- multiexp over the CALLER's record layout (strided records).  bellman keeps its CRS as `Arc<Vec<G1Affine>>` of
+ * `{ x: Fq, y: Fq, infinity: bool }` records (72 B; G2Affine 136 B, ec.rs:14-18) with the coordinates already in this ABI's form
+ * (Montgomery u64[4] little endian; G2: c0 || c1).  These entry points take such a vector as it lies in memory: record i starts at
+ * bases + i * stride; x is the 32 (G1) / 64 (G2) bytes at x_off, y those at y_off; when inf_off != MI355ZK_NO_FLAG and the byte at
+ * inf_off is non-zero the record is the identity whatever its coordinates hold, otherwise the coordinates are taken as they are
+ * (all-zero is still the identity).  The raw records cross PCIe in bounded pieces and are repacked on the device by the records_pack
+ * kernel (no host-side conversion, no host copy); the MSM kernels are those of the packed entry points.  Result, return codes and
+ * mi355zk_last_error_index are exactly those of mi355zk_bn254_g{1,2}_msm on the packed vector -- UnexpectedIdentity for a flagged base
+ * under a non-zero exponent, UnexpectedEof, the multi-device cells of mi355zk_init's device set.
+ * Returns 3 before any device work when: stride is 0, not a multiple of 4 or > 4096; x_off or y_off is not a multiple of 4; a
+ * coordinate runs past stride; the x and y ranges overlap; inf_off (unless MI355ZK_NO_FLAG) is >= stride or inside a coordinate; or for
+ * the limits of the packed form (NULL pointers, sizes >= 2^31).  stride 64 / 128, x_off 0, y_off 32 / 64, no flag IS the packed layout and
+ * takes the packed path unchanged. */
+#define MI355ZK_NO_FLAG ((size_t)-1)
+int mi355zk_bn254_g1_msm_strided(const void *bases, size_t n_bases, size_t stride, size_t x_off, size_t y_off, size_t inf_off,
+                                 size_t base_offset, const uint64_t *scalars, size_t n_scalars,
+                                 const uint32_t *density, size_t density_bits, uint64_t out_xyz[12]);
+int mi355zk_bn254_g2_msm_strided(const void *bases, size_t n_bases, size_t stride, size_t x_off, size_t y_off, size_t inf_off,
+                                 size_t base_offset, const uint64_t *scalars, size_t n_scalars,
+                                 const uint32_t *density, size_t density_bits, uint64_t out_xyz[24]);
+/* mi355zk_bases_cache_pin for a strided vector (same promise: the records are neither rewritten nor freed until
+ * mi355zk_bases_cache_invalidate(host_bases)).  The layout is part of the pin and of the cache entry: a vector pinned under one layout
+ * is served to strided calls with that layout only, and the same pointer pinned under two layouts is two entries.  The device copy
+ * is the PACKED vector (mi355zk_bases_cache_info reports n * 64 / n * 128 bytes).  flags: MI355ZK_PIN_TABLES also keeps the window
+ * table (as mi355zk_bases_cache_pin_tables).  mi355zk_bases_cache_invalidate(host_bases) drops every layout pinned there.  Returns 3
+ * for a bad layout (the rules above), a bad group, NULL / n_bases == 0, or unknown flag bits. */
+#define MI355ZK_PIN_TABLES 1u
+int mi355zk_bases_cache_pin_strided(const void *host_bases, size_t n_bases, size_t stride, size_t x_off, size_t y_off,
+                                    size_t inf_off, int group, uint32_t flags);
+/* The repack kernel on device-resident records: n raw records at d_raw (layout as above) -> n packed records at d_out (64 / 128 B
+ * each).  d_out must be 16-byte aligned and d_raw 4-byte aligned; the two may not overlap (3 otherwise).  Enqueued on `stream`
+ * (a hipStream_t, NULL = the default stream); returns without waiting. */
+int mi355zk_bn254_g1_records_pack_dev(const void *d_raw, size_t n, size_t stride, size_t x_off, size_t y_off, size_t inf_off,
+                                      void *d_out, void *stream);
+int mi355zk_bn254_g2_records_pack_dev(const void *d_raw, size_t n, size_t stride, size_t x_off, size_t y_off, size_t inf_off,
+                                      void *d_out, void *stream);
 
 /* ---- multiexp: bases and scalars already resident in HBM (the CRS / tau-table is reused across
  * calls: `Arc<Vec<G>>` inside groth16::Parameters, groth16/mod.rs:216-238).  `density` stays a HOST

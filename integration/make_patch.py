@@ -2,7 +2,7 @@
 """Regenerates integration/bellman_mi355zk.patch: copies /root/reference/bellman twice, applies the edits below to one copy (and drops
 integration/mi355zk.rs in as src/mi355zk.rs), and writes `diff -urN -U2` of the two trees with the timestamps stripped.  Needs the reference
 tree, so it runs in the build container only; tests/test_integration_patch.py checks the committed patch still applies (`patch --dry-run`).
-The edits are the whole Rust-side change a maintainer reviews: one feature line, one `mod`, two defaulted trait methods with their
+The edits are the whole Rust-side change a maintainer reviews: one feature line, one `mod`, three defaulted trait methods with their
 implementations, and one early return in each of `multiexp` and `best_fft`."""
 import os
 import shutil
@@ -21,10 +21,13 @@ EDITS = [
     ("src/source.rs", "    fn new(self) -> Self::Source;\n}\n",
      "    fn new(self) -> Self::Source;\n\n"
      "    /// The bases as one slice plus the cursor's start, when the source is one (mi355zk: what crosses the FFI boundary).\n"
-     "    fn as_contiguous(&self) -> Option<(&[G], usize)> {\n        None\n    }\n}\n"),
+     "    fn as_contiguous(&self) -> Option<(&[G], usize)> {\n        None\n    }\n\n"
+     "    /// The shared vector behind the source, when there is one: mi355zk pins it on the device and keeps this clone while it does.\n"
+     "    fn shared_bases(&self) -> Option<Arc<Vec<G>>> {\n        None\n    }\n}\n"),
     ("src/source.rs", "    fn new(self) -> (Arc<Vec<G>>, usize) {\n        (self.0.clone(), self.1)\n    }\n",
      "    fn new(self) -> (Arc<Vec<G>>, usize) {\n        (self.0.clone(), self.1)\n    }\n\n"
-     "    fn as_contiguous(&self) -> Option<(&[G], usize)> {\n        Some((&self.0[..], self.1))\n    }\n"),
+     "    fn as_contiguous(&self) -> Option<(&[G], usize)> {\n        Some((&self.0[..], self.1))\n    }\n\n"
+     "    fn shared_bases(&self) -> Option<Arc<Vec<G>>> {\n        Some(self.0.clone())\n    }\n"),
     ("src/source.rs", "    fn iter(self) -> Self::Iter;\n    fn get_query_size(self) -> Option<usize>;\n}\n",
      "    fn iter(self) -> Self::Iter;\n    fn get_query_size(self) -> Option<usize>;\n\n"
      "    /// The map as (u32 words: bit i = word i / 32, bit i % 32; number of bits); no words = every exponent has a base (mi355zk).\n"

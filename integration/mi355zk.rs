@@ -2,9 +2,11 @@
 //! functions, `multiexp::multiexp` (multiexp.rs:330-355) and `domain::best_fft` (domain.rs:263-272).
 //!
 //! Added by integration/bellman_mi355zk.patch together with five small hunks (Cargo.toml: the `mi355zk` feature; lib.rs: this module;
-//! source.rs: two defaulted trait methods; multiexp.rs / domain.rs: one early return each).  With the feature off nothing changes; with it
-//! on, BN254 G1 / G2 multiexps over `(Arc<Vec<G>>, usize)` sources and BN254 `Scalar` FFTs run on the MI355X and every other engine, source
-//! or element type falls through to the existing Rust path.  Return codes: 0 ok; 1 / 2 / 3 are the reference's own errors (`map_err`); a
+//! source.rs: three defaulted trait methods; multiexp.rs / domain.rs: one early return each).  With the feature off nothing changes; with
+//! it on, BN254 G1 / G2 multiexps over `(Arc<Vec<G>>, usize)` sources and BN254 `Scalar` FFTs run on the MI355X and every other engine,
+//! source or element type falls through to the existing Rust path.  The bases cross the boundary as they lie in the `Vec<G1Affine>` /
+//! `Vec<G2Affine>` (the strided entry points: the library repacks them on the device), and a shared vector is pinned on the device on
+//! first use, so the parameters of a prover are uploaded once per process (try_multiexp).  Return codes: 0 ok; 1 / 2 / 3 are the reference's own errors (`map_err`); a
 //! negative code is a DEVICE failure and means "fall through to the CPU path" -- a broken GPU never changes a result.
 //!
 //! This image has no rustc: the file is kept honest mechanically instead -- the `extern "C"` block below is GENERATED from the header
@@ -12,12 +14,12 @@
 //! argument count, and that the patch applies to the reference's bellman/ tree).
 #![allow(dead_code)]
 
-use std::any::TypeId;
+use std::any::{Any, TypeId};
 use std::io::{self, Write};
 use std::mem;
 use std::os::raw::{c_char, c_int, c_long, c_longlong, c_void};
 use std::ptr;
-use std::sync::Arc;
+use std::sync::{Arc, Mutex, Once};
 
 use futures::{future, Future};
 
@@ -30,12 +32,14 @@ use crate::source::{QueryDensity, SourceBuilder};
 use crate::SynthesisError;
 
 /// MI355ZK_ABI_VERSION of the header the block below was generated from; `abi_ok()` compares it with the loaded library's.
-pub const MI355ZK_ABI_VERSION: c_int = 6;
+pub const MI355ZK_ABI_VERSION: c_int = 7;
 // mode / flag bits (include/mi355zk.h)
 pub const MI355ZK_MSM_SCALARS_MONTGOMERY: u32 = 1; // msm_ex_dev / msm_table_dev `flags`: the exponents are Montgomery Fr (prover.rs:89-129 fused)
 pub const MI355ZK_EXP_SAME_SCALAR: c_int = 1; // batch_exp `mode`: ONE scalar for all points (phase2 contribute)
 pub const MI355ZK_FFT_INVERSE: c_int = 1; // point_fft `mode`: omega^-1 and the 1/m scaling
 pub const MI355ZK_G2_TRUSTED_SUBGROUP: c_int = 2; // batch_exp / point_fft / sparse_matvec: the caller's promise
+pub const MI355ZK_NO_FLAG: usize = usize::MAX; // msm_strided / pin_strided `inf_off`: the records carry no infinity flag
+pub const MI355ZK_PIN_TABLES: u32 = 1; // pin_strided `flags`: keep the window table too
 
 // ---- BEGIN GENERATED (tools/gen_rust_ffi.py from include/mi355zk.h) ----
 #[link(name = "mi355zk")]
@@ -52,6 +56,11 @@ extern "C" {
     pub fn mi355zk_bases_cache_invalidate(host_bases: *const c_void);
     pub fn mi355zk_bases_cache_info(host_bases: *const c_void, device_bytes: *mut usize, table_bytes: *mut usize) -> c_int;
     pub fn mi355zk_bn254_g2_msm(bases: *const u8, n_bases: usize, base_offset: usize, scalars: *const u64, n_scalars: usize, density: *const u32, density_bits: usize, out_xyz: *mut u64 /* [24] */) -> c_int;
+    pub fn mi355zk_bn254_g1_msm_strided(bases: *const c_void, n_bases: usize, stride: usize, x_off: usize, y_off: usize, inf_off: usize, base_offset: usize, scalars: *const u64, n_scalars: usize, density: *const u32, density_bits: usize, out_xyz: *mut u64 /* [12] */) -> c_int;
+    pub fn mi355zk_bn254_g2_msm_strided(bases: *const c_void, n_bases: usize, stride: usize, x_off: usize, y_off: usize, inf_off: usize, base_offset: usize, scalars: *const u64, n_scalars: usize, density: *const u32, density_bits: usize, out_xyz: *mut u64 /* [24] */) -> c_int;
+    pub fn mi355zk_bases_cache_pin_strided(host_bases: *const c_void, n_bases: usize, stride: usize, x_off: usize, y_off: usize, inf_off: usize, group: c_int, flags: u32) -> c_int;
+    pub fn mi355zk_bn254_g1_records_pack_dev(d_raw: *const c_void, n: usize, stride: usize, x_off: usize, y_off: usize, inf_off: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_bn254_g2_records_pack_dev(d_raw: *const c_void, n: usize, stride: usize, x_off: usize, y_off: usize, inf_off: usize, d_out: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_g1_msm_dev(d_bases: *const c_void, n_bases: usize, base_offset: usize, d_scalars: *const c_void, n_scalars: usize, density: *const u32, density_bits: usize, stream: *mut c_void, out_xyz: *mut u64 /* [12] */) -> c_int;
     pub fn mi355zk_bn254_g2_msm_dev(d_bases: *const c_void, n_bases: usize, base_offset: usize, d_scalars: *const c_void, n_scalars: usize, density: *const u32, density_bits: usize, stream: *mut c_void, out_xyz: *mut u64 /* [24] */) -> c_int;
     pub fn mi355zk_bn254_g1_dense_multiexp_dev(d_bases: *const c_void, d_scalars: *const c_void, n: usize, stream: *mut c_void, out_xyz: *mut u64 /* [12] */) -> c_int;
@@ -138,7 +147,6 @@ pub fn map_err(rc: c_int) -> Option<SynthesisError> {
 /// The library speaks the revision this file was generated against (argument MEANINGS changed between revisions -- batch_exp's and
 /// point_fft's `mode`, sparse_matvec's `flags` -- so a mismatch is a refusal, i.e. the CPU path, never a guess).  Checked once.
 pub fn abi_ok() -> bool {
-    use std::sync::Once;
     static CHECK: Once = Once::new();
     static mut OK: bool = false;
     unsafe {
@@ -220,10 +228,96 @@ fn g2_from_jacobian(xyz: &[u64]) -> G2 {
     enc.into_affine_unchecked().expect("a point the library returned").into_projective()
 }
 
+/// Where the fields of a bn256 affine type lie in memory: `{ x, y, infinity: bool }` (ec.rs:14-18) is 72 / 136 B, but Rust gives no
+/// layout guarantee for it, so it is PROBED once per process and never assumed.  `one()` and `zero()` are written into zero-initialised
+/// buffers of the type's size; x and y are where the packed record of `one()` (what g1_records / g2_records encode) occurs, and the
+/// flag is the byte outside them that is 0 in `one()` and non-zero in `zero()`.  Any of the three not found exactly once: `None`, and the
+/// shim keeps the packed-record path.
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct RecordLayout {
+    pub stride: usize,
+    pub x_off: usize,
+    pub y_off: usize,
+    pub inf_off: usize,
+}
+
+fn bytes_of<A: Copy>(a: &A) -> Vec<u8> {
+    let mut buf = vec![0u8; mem::size_of::<A>()];
+    unsafe { ptr::write_unaligned(buf.as_mut_ptr() as *mut A, *a) };
+    buf
+}
+
+fn find_once(hay: &[u8], needle: &[u8]) -> Option<usize> {
+    let mut hits = (0..=hay.len().saturating_sub(needle.len())).filter(|&i| hay.len() >= needle.len() && &hay[i..i + needle.len()] == needle);
+    let first = hits.next()?;
+    if hits.next().is_some() {
+        return None;
+    }
+    Some(first)
+}
+
+fn probe_layout<A: Copy>(one: &A, zero: &A, packed_one: &[u8]) -> Option<RecordLayout> {
+    let (a, z) = (bytes_of(one), bytes_of(zero));
+    let c = packed_one.len() / 2;
+    let x_off = find_once(&a, &packed_one[..c])?;
+    let y_off = find_once(&a, &packed_one[c..])?;
+    let inside = |i: usize| (i >= x_off && i < x_off + c) || (i >= y_off && i < y_off + c);
+    let mut flags = (0..a.len()).filter(|&i| !inside(i) && a[i] == 0 && z[i] != 0);
+    let inf_off = flags.next()?;
+    if flags.next().is_some() {
+        return None;
+    }
+    Some(RecordLayout { stride: a.len(), x_off, y_off, inf_off })
+}
+
+/// The probed layouts of G1Affine and G2Affine (once per process).
+pub fn affine_layouts() -> (Option<RecordLayout>, Option<RecordLayout>) {
+    static PROBE: Once = Once::new();
+    static mut LAYOUTS: (Option<RecordLayout>, Option<RecordLayout>) = (None, None);
+    unsafe {
+        PROBE.call_once(|| {
+            let g1 = probe_layout(&G1Affine::one(), &G1Affine::zero(), &g1_records(&[G1Affine::one()])[..]);
+            let g2 = probe_layout(&G2Affine::one(), &G2Affine::zero(), &g2_records(&[G2Affine::one()])[..]);
+            LAYOUTS = (g1, g2);
+        });
+        LAYOUTS
+    }
+}
+
+/// The base vectors pinned on the device: (address, length, a clone of the `Arc<Vec<G>>`).  The clone keeps the allocation alive and
+/// unchanged (an `Arc<Vec<G>>` with another owner cannot be mutated) -- the promise mi355zk_bases_cache_pin_strided asks for.  Once the
+/// registry holds the last reference (the caller dropped its Parameters), the entry is invalidated and dropped by the next call.
+static PINNED: Mutex<Vec<(usize, usize, Arc<dyn Any + Send + Sync>)>> = Mutex::new(Vec::new());
+
+fn pin_shared<G: CurveAffine>(v: Arc<Vec<G>>, lay: &RecordLayout, group: c_int) {
+    let mut pinned = match PINNED.lock() {
+        Ok(g) => g,
+        Err(_) => return,
+    };
+    pinned.retain(|(p, _, arc)| {
+        if Arc::strong_count(arc) > 1 {
+            return true;
+        }
+        unsafe { mi355zk_bases_cache_invalidate(*p as *const c_void) };
+        false
+    });
+    let (p, n) = (v.as_ptr() as usize, v.len());
+    if n == 0 || pinned.iter().any(|(q, m, _)| *q == p && *m == n) {
+        return;
+    }
+    let rc = unsafe { mi355zk_bases_cache_pin_strided(p as *const c_void, n, lay.stride, lay.x_off, lay.y_off, lay.inf_off, group, 0) };
+    if rc == 0 {
+        pinned.push((p, n, v as Arc<dyn Any + Send + Sync>));
+    }
+}
+
 /// The body of `multiexp` (multiexp.rs:330-355) on the device.  `None`: not a BN254 curve, not a contiguous source, an opaque density
-/// map, or a device failure -- the caller continues into `multiexp_inner_impl` unchanged.  A ready future is what
-/// `singlecore::Worker::compute` already returns (singlecore.rs:33-47); the library is re-entrant, so the prover's eight calls before
-/// the first `wait()` (prover.rs:250-298) may come from any threads.
+/// map, a record layout the library refuses, or a device failure -- the caller continues into `multiexp_inner_impl` unchanged.  A ready
+/// future is what `singlecore::Worker::compute` already returns (singlecore.rs:33-47); the library is re-entrant, so the prover's eight
+/// calls before the first `wait()` (prover.rs:250-298) may come from any threads.
+/// The bases go to the library as they lie in the caller's memory (mi355zk_bn254_g{1,2}_msm_strided, repacked on the device); a source
+/// that shares its `Arc<Vec<G>>` (the parameters of groth16, reused by every proof) is pinned on first use, so later calls over it send
+/// only the exponents.  Without a probed layout the records are encoded on the host (g1_records / g2_records), as before.
 pub fn try_multiexp<Q, D, G, S>(
     bases: &S,
     density_map: &D,
@@ -245,12 +339,33 @@ where
     // FrRepr is `pub struct FrRepr(pub [u64; 4])`: the exponent vector IS the ABI's scalar array
     let scalars = exponents.as_ptr() as *const u64;
     let mut out = [0u64; 24];
-    let rc = if is_g1 {
-        let raw = g1_records(unsafe { &*(slice as *const [G] as *const [G1Affine]) });
-        unsafe { mi355zk_bn254_g1_msm(raw.as_ptr(), slice.len(), offset, scalars, exponents.len(), density, bits, out.as_mut_ptr()) }
-    } else {
-        let raw = g2_records(unsafe { &*(slice as *const [G] as *const [G2Affine]) });
-        unsafe { mi355zk_bn254_g2_msm(raw.as_ptr(), slice.len(), offset, scalars, exponents.len(), density, bits, out.as_mut_ptr()) }
+    let (g1_lay, g2_lay) = affine_layouts();
+    let rc = match if is_g1 { g1_lay } else { g2_lay } {
+        Some(lay) => {
+            if let Some(v) = bases.shared_bases() {
+                pin_shared(v, &lay, if is_g1 { 1 } else { 2 });
+            }
+            let p = slice.as_ptr() as *const c_void;
+            let rc = unsafe {
+                if is_g1 {
+                    mi355zk_bn254_g1_msm_strided(p, slice.len(), lay.stride, lay.x_off, lay.y_off, lay.inf_off, offset, scalars, exponents.len(), density, bits, out.as_mut_ptr())
+                } else {
+                    mi355zk_bn254_g2_msm_strided(p, slice.len(), lay.stride, lay.x_off, lay.y_off, lay.inf_off, offset, scalars, exponents.len(), density, bits, out.as_mut_ptr())
+                }
+            };
+            if rc == 3 {
+                return None; // a layout the library refuses: the CPU path
+            }
+            rc
+        }
+        None if is_g1 => {
+            let raw = g1_records(unsafe { &*(slice as *const [G] as *const [G1Affine]) });
+            unsafe { mi355zk_bn254_g1_msm(raw.as_ptr(), slice.len(), offset, scalars, exponents.len(), density, bits, out.as_mut_ptr()) }
+        }
+        None => {
+            let raw = g2_records(unsafe { &*(slice as *const [G] as *const [G2Affine]) });
+            unsafe { mi355zk_bn254_g2_msm(raw.as_ptr(), slice.len(), offset, scalars, exponents.len(), density, bits, out.as_mut_ptr()) }
+        }
     };
     if rc == 0 {
         let p: <G as CurveAffine>::Projective = if is_g1 { same_type_copy(&g1_from_jacobian(&out)) } else { same_type_copy(&g2_from_jacobian(&out)) };

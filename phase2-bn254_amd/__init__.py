@@ -18,6 +18,7 @@ from .bellman import (  # noqa: F401
     EvaluationDomain,
     FullDensity,
     MsmTable,
+    StridedBases,
     SynthesisError,
     Worker,
     multiexp,

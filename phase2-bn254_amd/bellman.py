@@ -149,10 +149,64 @@ class _Ready:
         return self._value
 
 
+class StridedBases:
+    """A host base vector in the CALLER's record layout: `data` is (n, stride) u8, record i = data[i]; x / y are the 32 (G1) or 64 (G2,
+    c0 || c1) Montgomery bytes at x_off / y_off; inf_off is the offset of a flag byte that makes the record the identity when non-zero
+    (None: no flag).  multiexp / pin_bases / unpin_bases take it where a packed (n, 8) / (n, 16) array goes; the library repacks the
+    records on the device (mi355zk_bn254_g{1,2}_msm_strided, mi355zk_bases_cache_pin_strided)."""
+
+    def __init__(self, data, group: int, x_off: int, y_off: int, inf_off=None):
+        assert not _is_torch(data) and data.dtype == np.uint8 and data.ndim == 2 and data.flags["C_CONTIGUOUS"]
+        assert group in (1, 2)
+        self.data, self.group = data, group
+        self.stride, self.x_off, self.y_off = int(data.shape[1]), int(x_off), int(y_off)
+        self.inf_off = None if inf_off is None else int(inf_off)
+
+    def __len__(self):
+        return int(self.data.shape[0])
+
+    @property
+    def layout(self):
+        return (self.stride, self.x_off, self.y_off, _lib.NO_FLAG if self.inf_off is None else self.inf_off)
+
+    def ptr(self):
+        return self.data.ctypes.data_as(C.c_void_p)
+
+    @classmethod
+    def _affine_rust(cls, group: int, x, y, infinity, pad: int):
+        # pairing's `G1Affine { x: Fq, y: Fq, infinity: bool }` / G2Affine (ec.rs:14-18): the coordinates, the flag byte, padding to 8 B
+        limbs = 4 * group
+        x = np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, limbs)
+        y = np.ascontiguousarray(y, dtype=np.uint64).reshape(-1, limbs)
+        n, csz = x.shape[0], 32 * group
+        stride = 2 * csz + 8
+        data = np.full((n, stride), pad, dtype=np.uint8)
+        data[:, :csz] = x.view(np.uint8).reshape(n, csz)
+        data[:, csz:2 * csz] = y.view(np.uint8).reshape(n, csz)
+        data[:, 2 * csz] = np.asarray(infinity, dtype=bool).reshape(n) if infinity is not None else 0
+        return cls(data, group, 0, csz, 2 * csz)
+
+    @classmethod
+    def g1_affine_rust(cls, x, y, infinity=None, pad: int = 0) -> "StridedBases":
+        """72-byte records x || y || infinity || 7 padding bytes (value `pad`) from (n, 4) u64 x / y limbs and a boolean mask."""
+        return cls._affine_rust(1, x, y, infinity, pad)
+
+    @classmethod
+    def g2_affine_rust(cls, x, y, infinity=None, pad: int = 0) -> "StridedBases":
+        """136-byte records x.c0 || x.c1 || y.c0 || y.c1 || infinity || 7 padding bytes from (n, 8) u64 x / y limbs and a mask."""
+        return cls._affine_rust(2, x, y, infinity, pad)
+
+
 def pin_bases(arr, tables: bool = False) -> None:
     """mi355zk_bases_cache_pin: declare the HOST base vector `arr` ((n, 8) / (n, 16) u64, C-contiguous) immutable until
     unpin_bases(arr) -- the `Arc<Vec<G>>` of a Parameters object (groth16/mod.rs:216-238).  Host-buffer multiexps over it then
-    keep their uploaded copy on the device.  Without the promise every call uploads its bases again."""
+    keep their uploaded copy on the device.  Without the promise every call uploads its bases again.  A StridedBases pins under its
+    layout (mi355zk_bases_cache_pin_strided; the device copy is packed)."""
+    if isinstance(arr, StridedBases):
+        rc = _lib.load().mi355zk_bases_cache_pin_strided(arr.ptr(), len(arr), *arr.layout, arr.group, _lib.PIN_TABLES if tables else 0)
+        if rc != 0:
+            raise ValueError("mi355zk_bases_cache_pin_strided: bad arguments")
+        return
     assert not _is_torch(arr) and arr.flags["C_CONTIGUOUS"] and arr.dtype == np.uint64
     fn = _lib.load().mi355zk_bases_cache_pin_tables if tables else _lib.load().mi355zk_bases_cache_pin  # tables: + the window table (table mode)
     rc = fn(arr.ctypes.data_as(C.c_void_p), arr.shape[0], {8: 1, 16: 2}[arr.shape[1]])
@@ -162,6 +216,8 @@ def pin_bases(arr, tables: bool = False) -> None:
 
 def unpin_bases(arr=None) -> None:
     """mi355zk_bases_cache_invalidate: the promise ends (before rewriting or freeing the vector); None: every vector."""
+    if isinstance(arr, StridedBases):
+        arr = arr.data   # (every layout pinned at the pointer goes)
     _lib.load().mi355zk_bases_cache_invalidate(arr.ctypes.data_as(C.c_void_p) if arr is not None else None)
 
 
@@ -195,6 +251,7 @@ def multiexp(pool: Worker, bases, density_map, exponents, window_group=None, sca
     scalars_montgomery, device-resident data only: `exponents` are Montgomery-form Fr elements, i.e. the prover's vectors BEFORE
     scalars_into_representations / field_elements_into_representations (prover.rs:89-129); the conversion is fused into the call.)  `bases` = (array, offset) like `(Arc<Vec<G>>, usize)`:
     array of shape (n_bases, 8) u64 for G1Affine raw records or (n_bases, 16) for G2Affine;
+    or a StridedBases (host records in the caller's layout, e.g. pairing's 72-byte G1Affine);
     `exponents` = (n, 4) u64 canonical FrRepr; `density_map` = FullDensity() or a DensityTracker.
     Returns a ready future whose wait() yields the Jacobian X||Y||Z limbs (12 / 24 u64)."""
     arr, offset = bases
@@ -216,6 +273,14 @@ def multiexp(pool: Worker, bases, density_map, exponents, window_group=None, sca
             rc = fn(C.c_void_p(arr.table.data_ptr()), arr.n_bases, offset, C.c_void_p(exponents.data_ptr()), n_exp,
                     words.ctypes.data_as(C.c_void_p) if words is not None else None, dbits,
                     _lib.MSM_SCALARS_MONTGOMERY if scalars_montgomery else 0, _stream_ptr(), out.ctypes.data_as(C.c_void_p))
+    elif isinstance(arr, StridedBases):
+        if (window_group is not None and tuple(window_group) != (1, 0)) or scalars_montgomery:
+            raise ValueError("window groups / Montgomery scalars need device-resident inputs")
+        exponents = np.ascontiguousarray(exponents, dtype=np.uint64)
+        out = np.zeros(12 * arr.group, dtype=np.uint64)
+        fn = lib.mi355zk_bn254_g1_msm_strided if arr.group == 1 else lib.mi355zk_bn254_g2_msm_strided
+        rc = fn(arr.ptr(), len(arr), *arr.layout, offset, exponents.ctypes.data_as(C.c_void_p), n_exp,
+                words.ctypes.data_as(C.c_void_p) if words is not None else None, dbits, out.ctypes.data_as(C.c_void_p))
     elif _is_torch(arr):
         import torch
 

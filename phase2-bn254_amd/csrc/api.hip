@@ -344,6 +344,48 @@ int mi355zk_bn254_g2_msm(const uint8_t* bases, size_t n_bases, size_t base_offse
     return msm_host_entry<2>(bases, n_bases, base_offset, scalars, n_scalars, density, density_bits, out_xyz);
   });
 }
+int mi355zk_bn254_g1_msm_strided(const void* bases, size_t n_bases, size_t stride, size_t x_off, size_t y_off, size_t inf_off,
+                                 size_t base_offset, const uint64_t* scalars, size_t n_scalars, const uint32_t* density, size_t density_bits,
+                                 uint64_t out_xyz[12]) {
+  return abi_guard([&]() -> int {
+    RecordLayout L;
+    if (records_layout_check(1, stride, x_off, y_off, inf_off, &L) != ZK_OK) { t_last_err_index = -1; return ZK_ERR_BAD_ARGS; }
+    return msm_host_entry<1>((const uint8_t*)bases, n_bases, base_offset, scalars, n_scalars, density, density_bits, out_xyz, L);
+  });
+}
+int mi355zk_bn254_g2_msm_strided(const void* bases, size_t n_bases, size_t stride, size_t x_off, size_t y_off, size_t inf_off,
+                                 size_t base_offset, const uint64_t* scalars, size_t n_scalars, const uint32_t* density, size_t density_bits,
+                                 uint64_t out_xyz[24]) {
+  return abi_guard([&]() -> int {
+    RecordLayout L;
+    if (records_layout_check(2, stride, x_off, y_off, inf_off, &L) != ZK_OK) { t_last_err_index = -1; return ZK_ERR_BAD_ARGS; }
+    return msm_host_entry<2>((const uint8_t*)bases, n_bases, base_offset, scalars, n_scalars, density, density_bits, out_xyz, L);
+  });
+}
+int mi355zk_bases_cache_pin_strided(const void* host_bases, size_t n_bases, size_t stride, size_t x_off, size_t y_off, size_t inf_off, int group,
+                                    uint32_t flags) {
+  return abi_guard([&]() -> int {
+    RecordLayout L;
+    if ((flags & ~MI355ZK_PIN_TABLES) || records_layout_check(group, stride, x_off, y_off, inf_off, &L) != ZK_OK) return ZK_ERR_BAD_ARGS;
+    return bases_cache_pin(host_bases, n_bases, group, (flags & MI355ZK_PIN_TABLES) != 0, L);
+  });
+}
+static int records_pack_dev(int group, const void* d_raw, size_t n, size_t stride, size_t x_off, size_t y_off, size_t inf_off, void* d_out,
+                            void* stream) {
+  RecordLayout L;
+  if (records_layout_check(group, stride, x_off, y_off, inf_off, &L) != ZK_OK) return ZK_ERR_BAD_ARGS;
+  if (n == 0) return ZK_OK;
+  if (!d_raw || !d_out || n >= (1ull << 31) || (uintptr_t)d_out % 16 || (uintptr_t)d_raw % 4) return ZK_ERR_BAD_ARGS;
+  const uintptr_t r0 = (uintptr_t)d_raw, r1 = r0 + n * stride, o0 = (uintptr_t)d_out, o1 = o0 + n * (group == 1 ? 64 : 128);
+  if (r0 < o1 && o0 < r1) return ZK_ERR_BAD_ARGS;  // d_out may not alias d_raw
+  return records_pack_run(group, d_raw, n, L, d_out, (hipStream_t)stream);
+}
+int mi355zk_bn254_g1_records_pack_dev(const void* d_raw, size_t n, size_t stride, size_t x_off, size_t y_off, size_t inf_off, void* d_out, void* stream) {
+  return abi_guard([&]() -> int { return records_pack_dev(1, d_raw, n, stride, x_off, y_off, inf_off, d_out, stream); });
+}
+int mi355zk_bn254_g2_records_pack_dev(const void* d_raw, size_t n, size_t stride, size_t x_off, size_t y_off, size_t inf_off, void* d_out, void* stream) {
+  return abi_guard([&]() -> int { return records_pack_dev(2, d_raw, n, stride, x_off, y_off, inf_off, d_out, stream); });
+}
 int mi355zk_bn254_g1_msm_dev(const void* d_bases, size_t n_bases, size_t base_offset, const void* d_scalars, size_t n_scalars,
                              const uint32_t* density, size_t density_bits, void* stream, uint64_t out_xyz[12]) {
   return abi_guard([&]() -> int {

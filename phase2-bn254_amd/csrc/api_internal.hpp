@@ -1,7 +1,7 @@
 // Internal interfaces between the translation units of libmi355zk.so (not part of the C ABI: include/mi355zk.h is).
 //   api.hip         the C ABI: argument checking, domain constants, device-resident entry points, profiling hooks, lifecycle
 //   scalar_mul.hip  the scalar-multiplication kernels and their launchers: batch_exp / batch_mul / window-table build / G2 membership
-//   (msm_g1.hip, msm_g2.hip, ntt.hip, point_fft*.hip, codec.hip, field_ops.hip: the kernels behind the functions declared below)
+//   (msm_g1.hip, msm_g2.hip, ntt.hip, point_fft*.hip, codec.hip, field_ops.hip, records.hip: the kernels behind the functions declared below)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -67,6 +67,21 @@ bool g2_in_subgroup_host(const Affine<Fq2>& p);   // the membership test of the 
 void exp_scratch_release_all();
 void mul_slots_release_all();
 
+// records.hip: base vectors in the CALLER's record layout (bellman's `G1Affine { x, y, infinity: bool }` is 72 B, G2Affine 136 B).
+// stride == 0 is the packed layout of the group (64 / 128 B, x || y, no flag).  Every non-packed layout passed below has been checked by
+// records_layout_check (coordinate ranges inside the record, disjoint, 4-byte aligned; the flag byte outside them).
+struct RecordLayout {
+  size_t stride = 0, x_off = 0, y_off = 0, inf_off = (size_t)-1;
+  bool packed() const { return stride == 0; }
+  size_t host_stride(int group) const { return stride ? stride : (group == 1 ? 64 : 128); }
+  bool operator==(const RecordLayout& o) const { return stride == o.stride && x_off == o.x_off && y_off == o.y_off && inf_off == o.inf_off; }
+  bool operator!=(const RecordLayout& o) const { return !(*this == o); }
+};
+// the ABI's argument rules (include/mi355zk.h: rc 3) -> ZK_OK and *out (the packed layout normalised to stride 0), or ZK_ERR_BAD_ARGS
+int records_layout_check(int group, size_t stride, size_t x_off, size_t y_off, size_t inf_off, RecordLayout* out);
+// n raw records at d_raw -> n packed records at d_out (the records_pack kernel, enqueued on `st`; no synchronisation)
+int records_pack_run(int group, const void* d_raw, size_t n, const RecordLayout& L, void* d_out, hipStream_t st);
+
 // api.hip
 int domain_op_dev(Fr* d_a, uint32_t log_n, int op, hipStream_t st);   // EvaluationDomain::{fft, ifft, coset_fft, icoset_fft} on a device array
 
@@ -85,7 +100,7 @@ int msm_dev_entry(const void* d_bases, size_t n_bases, size_t base_offset, const
 // host buffers: whole on one device (streamed upload, pinned-bases cache) or cut into cells over the device set of mi355zk_init
 template <int GROUP>
 int msm_host_entry(const uint8_t* bases, size_t n_bases, size_t base_offset, const uint64_t* scalars, size_t n_scalars, const uint32_t* density,
-                   size_t density_bits, uint64_t* out_xyz);
+                   size_t density_bits, uint64_t* out_xyz, const RecordLayout& L = RecordLayout());
 template <class F>
 int batch_exp_host(uint8_t* out, const uint8_t* bases, const uint64_t* scalars, size_t n, int same_scalar, bool g2_trusted);
 template <int GROUP>
@@ -99,8 +114,8 @@ int sparse_matvec_host(uint8_t* out, const uint8_t* bases, size_t n_bases, const
                        size_t n_rows, size_t nnz, int group, bool g2_trusted);
 extern template int msm_dev_entry<1>(const void*, size_t, size_t, const void*, size_t, const uint32_t*, size_t, void*, uint64_t*, uint32_t, uint32_t, uint32_t, MsmChunks*, bool);
 extern template int msm_dev_entry<2>(const void*, size_t, size_t, const void*, size_t, const uint32_t*, size_t, void*, uint64_t*, uint32_t, uint32_t, uint32_t, MsmChunks*, bool);
-extern template int msm_host_entry<1>(const uint8_t*, size_t, size_t, const uint64_t*, size_t, const uint32_t*, size_t, uint64_t*);
-extern template int msm_host_entry<2>(const uint8_t*, size_t, size_t, const uint64_t*, size_t, const uint32_t*, size_t, uint64_t*);
+extern template int msm_host_entry<1>(const uint8_t*, size_t, size_t, const uint64_t*, size_t, const uint32_t*, size_t, uint64_t*, const RecordLayout&);
+extern template int msm_host_entry<2>(const uint8_t*, size_t, size_t, const uint64_t*, size_t, const uint32_t*, size_t, uint64_t*, const RecordLayout&);
 extern template int batch_exp_host<Fq>(uint8_t*, const uint8_t*, const uint64_t*, size_t, int, bool);
 extern template int batch_exp_host<Fq2>(uint8_t*, const uint8_t*, const uint64_t*, size_t, int, bool);
 extern template int dense_host<1>(const uint8_t*, const uint8_t*, const uint64_t*, size_t, uint64_t*, uint64_t*);
@@ -109,7 +124,8 @@ extern template int sparse_matvec<Fq>(void*, const void*, size_t, const uint32_t
 extern template int sparse_matvec<Fq2>(void*, const void*, size_t, const uint32_t*, const uint32_t*, const void*, size_t, size_t, void*, int, bool, void*, size_t);
 extern template int sparse_matvec_host<Fq>(uint8_t*, const uint8_t*, size_t, const uint32_t*, const uint32_t*, const uint64_t*, size_t, size_t, int, bool);
 extern template int sparse_matvec_host<Fq2>(uint8_t*, const uint8_t*, size_t, const uint32_t*, const uint32_t*, const uint64_t*, size_t, size_t, int, bool);
-int bases_cache_pin(const void* host, size_t n, int group, bool tables = false);   // the caller's promise of immutability (include/mi355zk.h)
+// the caller's promise of immutability (include/mi355zk.h); lay: the records' layout (part of the pin and of the cache key)
+int bases_cache_pin(const void* host, size_t n, int group, bool tables = false, const RecordLayout& lay = RecordLayout());
 void bases_cache_invalidate(const void* host);
 int bases_cache_info(const void* host_bases, size_t* device_bytes, size_t* table_bytes);
 void devset_set(const std::vector<int>& set);   // the device set of mi355zk_init (empty: the current device)

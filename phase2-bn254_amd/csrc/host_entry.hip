@@ -200,9 +200,10 @@ struct BasesEntry {
   const void* owner = nullptr;  // the pinned vector the records belong to (== host unless a slice): what invalidate / info are asked about
   size_t n = 0;
   int group = 0, dev = 0;
+  RecordLayout lay;        // the host records' layout (part of the key: the device copy is always packed)
   uint64_t fp = 0;
   void* d = nullptr;
-  size_t bytes = 0;
+  size_t bytes = 0;        // of the packed device copy
   uint64_t tick = 0;
   bool ready = false;      // fully uploaded
   std::mutex fill_mu;      // held by the call that uploads it
@@ -245,21 +246,22 @@ struct BasesPin {
   size_t n;
   int group;
   bool tables;
+  RecordLayout lay;
 };
 std::vector<BasesPin> g_bc_pins;  // under g_bc_mu
 bool bases_cache_implicit() {
   static const char* env = std::getenv("MI355ZK_BASES_CACHE_IMPLICIT");
   return env && env[0] == '1';
 }
-int bases_cache_pin(const void* host, size_t n, int group, bool tables) {
+int bases_cache_pin(const void* host, size_t n, int group, bool tables, const RecordLayout& lay) {
   if (!host || n == 0 || (group != 1 && group != 2)) return ZK_ERR_BAD_ARGS;
   std::lock_guard<std::mutex> lk(g_bc_mu);
   for (auto& p : g_bc_pins)
-    if (p.host == host && p.n == n && p.group == group) {
+    if (p.host == host && p.n == n && p.group == group && p.lay == lay) {
       p.tables = p.tables || tables;
       return ZK_OK;
     }
-  g_bc_pins.push_back(BasesPin{host, n, group, tables});
+  g_bc_pins.push_back(BasesPin{host, n, group, tables, lay});
   return ZK_OK;
 }
 // returns the entry (locked for filling when *fill == true: the caller uploads and then sets ready) or nullptr (cache off / not
@@ -268,7 +270,8 @@ int bases_cache_pin(const void* host, size_t n, int group, bool tables) {
 // slice, so that mi355zk_bases_cache_invalidate(vector) reaches the slices on every device (a pinned vector's slices find
 // their owner in the pin list)
 thread_local const void* t_bases_parent = nullptr;
-std::shared_ptr<BasesEntry> bases_lookup(const void* host, size_t n, int group, size_t bytes, int dev, bool* fill) {
+// bytes: of the packed device copy; the host records are n * lay.host_stride(group) bytes
+std::shared_ptr<BasesEntry> bases_lookup(const void* host, size_t n, int group, size_t bytes, int dev, bool* fill, const RecordLayout& lay) {
   *fill = false;
   const size_t cap = bases_cache_cap();
   if (cap == 0 || bytes > cap) return nullptr;
@@ -279,9 +282,9 @@ std::shared_ptr<BasesEntry> bases_lookup(const void* host, size_t n, int group, 
     // pinned: the vector itself, or a record range INSIDE a pinned vector (the single-process multi-GPU mode caches on each device only
     // the slice its cell consumes: SURVEY 8e "the tau-table slice stays resident on its GPU")
     bool pinned = false;
-    const size_t rec = group == 1 ? 64 : 128;
+    const size_t rec = lay.host_stride(group);
     for (auto& p : g_bc_pins) {
-      if (p.group != group) continue;
+      if (p.group != group || p.lay != lay) continue;
       const char* lo = (const char*)p.host;
       if ((const char*)host >= lo && (const char*)host + n * rec <= lo + p.n * rec) {
         pinned = true;
@@ -291,12 +294,13 @@ std::shared_ptr<BasesEntry> bases_lookup(const void* host, size_t n, int group, 
     }
     if (!pinned && !bases_cache_implicit()) return nullptr;
   }
-  const uint64_t fp = bases_fingerprint((const uint8_t*)host, bytes, group == 1 ? 64 : 128);
+  const size_t rec = lay.host_stride(group);  // (strided: whole records are sampled, the flag byte included)
+  const uint64_t fp = bases_fingerprint((const uint8_t*)host, n * rec, rec);
   std::shared_ptr<BasesEntry> hit;
   {
     std::lock_guard<std::mutex> lk(g_bc_mu);
     for (auto& e : g_bc)
-      if (e->host == host && e->n == n && e->group == group && e->dev == dev && e->fp == fp) { hit = e; break; }
+      if (e->host == host && e->n == n && e->group == group && e->lay == lay && e->dev == dev && e->fp == fp) { hit = e; break; }
     if (hit) { hit->tick = ++g_bc_tick; hit->want_table = hit->want_table || want_table; }
   }
   if (hit) {
@@ -305,7 +309,7 @@ std::shared_ptr<BasesEntry> bases_lookup(const void* host, size_t n, int group, 
     return nullptr;                                       // its upload failed: go uncached
   }
   auto e = std::make_shared<BasesEntry>();
-  e->host = host; e->owner = owner; e->n = n; e->group = group; e->dev = dev; e->fp = fp; e->bytes = bytes; e->want_table = want_table;
+  e->host = host; e->owner = owner; e->n = n; e->group = group; e->lay = lay; e->dev = dev; e->fp = fp; e->bytes = bytes; e->want_table = want_table;
   {
     std::lock_guard<std::mutex> lk(g_bc_mu);
     // the capacity is PER DEVICE (a process may drive several: mi355zk_init with n_devices > 1 keeps a copy of a pinned vector on
@@ -353,6 +357,8 @@ struct HostStage {
   size_t sc_bytes = 0;
   void* bases = nullptr;
   size_t bases_bytes = 0;
+  void* raw = nullptr;      // strided records: one bounded piece of the caller's raw records on its way to records_pack
+  size_t raw_bytes = 0;
   hipStream_t copy = nullptr, compute = nullptr;
 };
 std::mutex g_stage_mu;
@@ -434,9 +440,9 @@ void host_entry_release_all() {
   std::lock_guard<std::mutex> lk(g_stage_mu);
   for (HostStage* s : g_stages) {
     (void)hipSetDevice(s->dev);
-    (void)hipFree(s->sc[0]); (void)hipFree(s->sc[1]); (void)hipFree(s->bases);
-    s->sc[0] = s->sc[1] = s->bases = nullptr;
-    s->sc_bytes = s->bases_bytes = 0;
+    (void)hipFree(s->sc[0]); (void)hipFree(s->sc[1]); (void)hipFree(s->bases); (void)hipFree(s->raw);
+    s->sc[0] = s->sc[1] = s->bases = s->raw = nullptr;
+    s->sc_bytes = s->bases_bytes = s->raw_bytes = 0;
   }
   std::lock_guard<std::mutex> dl(DensityPool::mu());
   for (DensityPool::Buf* b : DensityPool::all()) {
@@ -486,14 +492,17 @@ constexpr uint64_t HOST_CHUNK_MIN = 1ull << 21;     // smallest first chunk of a
 
 // One host-buffer multiexp on the calling thread's CURRENT device.  (wgroups, wgroup): only that group of scalar windows (a cell of
 // the single-process multi-GPU mode below; (1, 0) is the whole multiexp).
+// L: the layout of the host records (packed by default; strided records are repacked on the device as they arrive).
 template <int GROUP>
 int msm_host_run(const uint8_t* bases, size_t n_bases, size_t base_offset, const uint64_t* scalars, size_t n_scalars,
-                 const uint32_t* density, size_t density_bits, uint64_t* out_xyz, uint32_t wgroups = 1, uint32_t wgroup = 0) {
+                 const uint32_t* density, size_t density_bits, uint64_t* out_xyz, const RecordLayout& L = RecordLayout(),
+                 uint32_t wgroups = 1, uint32_t wgroup = 0) {
   t_last_err_index = -1;
   if (!out_xyz || (n_scalars && !scalars) || (n_bases && !bases)) return ZK_ERR_BAD_ARGS;
   if (n_bases >= (1ull << 31) || n_scalars >= (1ull << 31)) return ZK_ERR_BAD_ARGS;
   constexpr size_t bsz = GROUP == 1 ? 64 : 128;
   constexpr size_t jac_words = GROUP == 1 ? 12 : 24;
+  const size_t hs = L.host_stride(GROUP);  // bytes per HOST record
   int dev = 0;
   ZK_HIP(hipGetDevice(&dev));
   StageLease stage_lease;
@@ -522,7 +531,7 @@ int msm_host_run(const uint8_t* bases, size_t n_bases, size_t base_offset, const
 
   // ---- bases: cached, being cached by this call, or (not pinned / cache off / full) the leased stage's buffer
   bool fill = false;
-  std::shared_ptr<BasesEntry> entry = n_bases ? bases_lookup(bases, n_bases, GROUP, n_bases * bsz, dev, &fill) : nullptr;
+  std::shared_ptr<BasesEntry> entry = n_bases ? bases_lookup(bases, n_bases, GROUP, n_bases * bsz, dev, &fill, L) : nullptr;
   void* d_bases = entry ? entry->d : nullptr;
   bool upload_bases = fill;
   if (!entry && n_bases) {
@@ -541,6 +550,26 @@ int msm_host_run(const uint8_t* bases, size_t n_bases, size_t base_offset, const
       if (!ok) bases_drop(e);
     }
   } guard{entry, fill};
+  // bases [lo, hi) -> d_bases, enqueued on the copy stream.  Packed records go straight over the link.  Strided records go raw, in pieces of
+  // at most RAW_PIECE records, into the stage's raw buffer, and records_pack repacks each piece into d_bases behind its copy; the copy
+  // stream's order keeps a piece from overwriting the raw buffer before the previous piece's repack has read it.  The device memory on
+  // top of the packed copy is one piece, not the vector.
+  constexpr uint64_t RAW_PIECE = 1ull << 19;
+  if (!L.packed() && n_bases && upload_bases) {
+    rc = stage_reserve(&S->raw, &S->raw_bytes, (size_t)std::min<uint64_t>(n_bases, RAW_PIECE) * hs);
+    if (rc) return rc;
+  }
+  auto put_bases = [&](uint64_t lo, uint64_t hi) -> hipError_t {
+    if (hi <= lo) return hipSuccess;
+    if (L.packed()) return hipMemcpyAsync((char*)d_bases + lo * bsz, bases + lo * bsz, (hi - lo) * bsz, hipMemcpyHostToDevice, S->copy);
+    for (uint64_t p = lo; p < hi; p += RAW_PIECE) {
+      const uint64_t m = std::min<uint64_t>(RAW_PIECE, hi - p);
+      hipError_t e = hipMemcpyAsync(S->raw, bases + p * hs, m * hs, hipMemcpyHostToDevice, S->copy);
+      if (e != hipSuccess) return e;
+      if (records_pack_run(GROUP, S->raw, m, L, (char*)d_bases + p * bsz, S->copy) != ZK_OK) return hipErrorLaunchFailure;
+    }
+    return hipSuccess;
+  };
 
   // ---- chunks (cut at multiples of 32 exponents, so that density words are not shared between chunks).  Every chunk runs digits ->
   // partition -> accumulate into the ONE bucket array of the call (msm_device, MsmChunks); what a chunk costs on top of its share
@@ -656,7 +685,7 @@ int msm_host_run(const uint8_t* bases, size_t n_bases, size_t base_offset, const
         uint64_t b_hi = base_offset + rank_of(hi);
         if (b_hi > n_bases) b_hi = n_bases;
         if (b_hi > b_done) {
-          e = hipMemcpyAsync((char*)d_bases + b_done * bsz, bases + b_done * bsz, (b_hi - b_done) * bsz, hipMemcpyHostToDevice, S->copy);
+          e = put_bases(b_done, b_hi);
           b_done = b_hi;
         }
       }
@@ -669,9 +698,8 @@ int msm_host_run(const uint8_t* bases, size_t n_bases, size_t base_offset, const
     }
     if (upload_bases && entry) {  // the rest of the vector (not needed by this call) completes the cache entry
       hipError_t e = hipSuccess;
-      if (b_lo > 0) e = hipMemcpyAsync(d_bases, bases, b_lo * bsz, hipMemcpyHostToDevice, S->copy);
-      if (e == hipSuccess && b_done < n_bases)
-        e = hipMemcpyAsync((char*)d_bases + b_done * bsz, bases + b_done * bsz, (n_bases - b_done) * bsz, hipMemcpyHostToDevice, S->copy);
+      if (b_lo > 0) e = put_bases(0, b_lo);
+      if (e == hipSuccess && b_done < n_bases) e = put_bases(b_done, n_bases);
       if (e == hipSuccess) e = hipStreamSynchronize(S->copy);
       if (e != hipSuccess) fail();
     }
@@ -711,7 +739,7 @@ int msm_host_run(const uint8_t* bases, size_t n_bases, size_t base_offset, const
     if (feed.copy_failed) result = ZK_ERR_DEVICE;
   } else if (upload_bases && entry && n_bases) {
     // nothing to evaluate, but the entry was created: fill it
-    hipError_t e = hipMemcpyAsync(d_bases, bases, n_bases * bsz, hipMemcpyHostToDevice, S->copy);
+    hipError_t e = put_bases(0, n_bases);
     if (e == hipSuccess) e = hipStreamSynchronize(S->copy);
     if (e != hipSuccess) result = ZK_ERR_DEVICE;
     if (result == ZK_OK && P.eof_index >= 0) { result = ZK_ERR_UNEXPECTED_EOF; err_idx = P.eof_index; }
@@ -779,7 +807,7 @@ uint64_t density_rank(const DensityPlan& P, const uint32_t* density, uint64_t i)
 
 template <int GROUP>
 int msm_host_multi(const std::vector<int>& devs, const uint8_t* bases, size_t n_bases, size_t base_offset, const uint64_t* scalars,
-                   size_t n_scalars, const uint32_t* density, size_t density_bits, uint64_t* out_xyz) {
+                   size_t n_scalars, const uint32_t* density, size_t density_bits, uint64_t* out_xyz, const RecordLayout& L) {
   using J = typename std::conditional<GROUP == 1, G1Jacobian, G2Jacobian>::type;
   t_last_err_index = -1;
   DensityPlan P;
@@ -829,15 +857,15 @@ int msm_host_multi(const std::vector<int>& devs, const uint8_t* bases, size_t n_
     // its device allocates, uploads and (inside a pinned vector) keeps: 2^26 G1 points on 8 devices are 512 MiB per device, not 4 GiB
     // (SURVEY 8e).  The ranges end before the first exponent without a base (the Eof is planned above for the whole call), so the slice
     // holds every base the cell asks for.
-    constexpr size_t bsz = GROUP == 1 ? 64 : 128;
+    const size_t hs = L.host_stride(GROUP);  // bytes per host record
     const uint64_t boff = base_offset + density_rank(P, density, c.lo);
     const uint64_t used = density_rank(P, density, c.hi) - density_rank(P, density, c.lo);
     struct ParentScope {
       explicit ParentScope(const void* p) { t_bases_parent = p; }
       ~ParentScope() { t_bases_parent = nullptr; }
     } parent_scope(bases);
-    c.rc = msm_host_run<GROUP>(bases + boff * bsz, used, 0, scalars + c.lo * 4, c.hi - c.lo, density ? density + (c.lo >> 5) : nullptr,
-                               density ? c.hi - c.lo : 0, reinterpret_cast<uint64_t*>(&c.part), wg, c.wgi);
+    c.rc = msm_host_run<GROUP>(bases + boff * hs, used, 0, scalars + c.lo * 4, c.hi - c.lo, density ? density + (c.lo >> 5) : nullptr,
+                               density ? c.hi - c.lo : 0, reinterpret_cast<uint64_t*>(&c.part), L, wg, c.wgi);
     c.err = t_last_err_index;
     if (trace)
       std::fprintf(stderr, "[mi355zk] multi: cell [%llu, %llu) window group %u/%u on device %d: rc %d at %.2f ms\n", (unsigned long long)c.lo,
@@ -885,9 +913,9 @@ int msm_host_multi(const std::vector<int>& devs, const uint8_t* bases, size_t n_
 // the host-buffer entry points: whole on one device, or cut into cells over the device set
 template <int GROUP>
 int msm_host_entry(const uint8_t* bases, size_t n_bases, size_t base_offset, const uint64_t* scalars, size_t n_scalars,
-                   const uint32_t* density, size_t density_bits, uint64_t* out_xyz) {
+                   const uint32_t* density, size_t density_bits, uint64_t* out_xyz, const RecordLayout& L) {
   const std::vector<int> devs = devset_snapshot();
-  if (devs.size() <= 1) return msm_host_run<GROUP>(bases, n_bases, base_offset, scalars, n_scalars, density, density_bits, out_xyz);
+  if (devs.size() <= 1) return msm_host_run<GROUP>(bases, n_bases, base_offset, scalars, n_scalars, density, density_bits, out_xyz, L);
   if (!out_xyz || (n_scalars && !scalars) || (n_bases && !bases) || n_bases >= (1ull << 31) || n_scalars >= (1ull << 31)) {
     t_last_err_index = -1;
     return ZK_ERR_BAD_ARGS;
@@ -895,7 +923,7 @@ int msm_host_entry(const uint8_t* bases, size_t n_bases, size_t base_offset, con
   const char* env = std::getenv("MI355ZK_MULTI_MIN_LOG");  // (read per call: the tests lower it)
   const int min_log = env ? std::atoi(env) : 20;
   if (n_scalars >= (1ull << (min_log < 0 ? 0 : min_log > 30 ? 30 : min_log)) && n_scalars >= 64)
-    return msm_host_multi<GROUP>(devs, bases, n_bases, base_offset, scalars, n_scalars, density, density_bits, out_xyz);
+    return msm_host_multi<GROUP>(devs, bases, n_bases, base_offset, scalars, n_scalars, density, density_bits, out_xyz, L);
   // A short call runs whole on ONE device: the one that already holds the (pinned) vector if there is one -- the device copy of a
   // parameter vector is then made once per process, not once per device of the set (8 x 4 GiB for a 2^26-point CRS) -- else the next in
   // turn, so that the prover's concurrent multiexps over its different vectors spread over the node on first touch.
@@ -903,12 +931,12 @@ int msm_host_entry(const uint8_t* bases, size_t n_bases, size_t base_offset, con
   {
     std::lock_guard<std::mutex> lk(g_bc_mu);
     for (auto& e : g_bc)
-      if (e->host == bases && e->n == n_bases && e->group == GROUP && std::find(devs.begin(), devs.end(), e->dev) != devs.end()) { pick = e->dev; break; }
+      if (e->host == bases && e->n == n_bases && e->group == GROUP && e->lay == L && std::find(devs.begin(), devs.end(), e->dev) != devs.end()) { pick = e->dev; break; }
   }
   if (pick < 0) pick = devs[g_devset_turn.fetch_add(1) % devs.size()];
   DeviceGuard guard;
   ZK_HIP(hipSetDevice(pick));
-  return msm_host_run<GROUP>(bases, n_bases, base_offset, scalars, n_scalars, density, density_bits, out_xyz);
+  return msm_host_run<GROUP>(bases, n_bases, base_offset, scalars, n_scalars, density, density_bits, out_xyz, L);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1316,8 +1344,8 @@ int bases_cache_info(const void* host_bases, size_t* device_bytes, size_t* table
 
 template int msm_dev_entry<1>(const void*, size_t, size_t, const void*, size_t, const uint32_t*, size_t, void*, uint64_t*, uint32_t, uint32_t, uint32_t, MsmChunks*, bool);
 template int msm_dev_entry<2>(const void*, size_t, size_t, const void*, size_t, const uint32_t*, size_t, void*, uint64_t*, uint32_t, uint32_t, uint32_t, MsmChunks*, bool);
-template int msm_host_entry<1>(const uint8_t*, size_t, size_t, const uint64_t*, size_t, const uint32_t*, size_t, uint64_t*);
-template int msm_host_entry<2>(const uint8_t*, size_t, size_t, const uint64_t*, size_t, const uint32_t*, size_t, uint64_t*);
+template int msm_host_entry<1>(const uint8_t*, size_t, size_t, const uint64_t*, size_t, const uint32_t*, size_t, uint64_t*, const RecordLayout&);
+template int msm_host_entry<2>(const uint8_t*, size_t, size_t, const uint64_t*, size_t, const uint32_t*, size_t, uint64_t*, const RecordLayout&);
 template int batch_exp_host<Fq>(uint8_t*, const uint8_t*, const uint64_t*, size_t, int, bool);
 template int batch_exp_host<Fq2>(uint8_t*, const uint8_t*, const uint64_t*, size_t, int, bool);
 template int dense_host<1>(const uint8_t*, const uint8_t*, const uint64_t*, size_t, uint64_t*, uint64_t*);

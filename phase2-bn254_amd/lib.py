@@ -15,7 +15,8 @@ SO_PATH = os.environ.get("MI355ZK_SO") or os.path.join(_HERE, "libmi355zk.so")
 OK, ERR_UNEXPECTED_IDENTITY, ERR_UNEXPECTED_EOF, ERR_BAD_ARGS, ERR_DEVICE = 0, 1, 2, 3, -1
 OP_FFT, OP_IFFT, OP_COSET_FFT, OP_ICOSET_FFT = 0, 1, 2, 3
 MSM_SCALARS_MONTGOMERY = 1
-ABI_VERSION = 6   # MI355ZK_ABI_VERSION of the include/mi355zk.h this table was written against: load() refuses another library
+NO_FLAG, PIN_TABLES = (1 << 64) - 1, 1   # MI355ZK_NO_FLAG (inf_off: no infinity flag byte) / MI355ZK_PIN_TABLES (include/mi355zk.h)
+ABI_VERSION = 7   # MI355ZK_ABI_VERSION of the include/mi355zk.h this table was written against: load() refuses another library
 EXP_SAME_SCALAR, FFT_INVERSE, G2_TRUSTED_SUBGROUP = 1, 1, 2   # mode / flag bits of batch_exp, point_fft, sparse_matvec (include/mi355zk.h)
 
 _vp, _sz, _i, _u32 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32
@@ -35,6 +36,11 @@ SIGNATURES = {
     "mi355zk_bases_cache_invalidate": (None, [_vp]),
     "mi355zk_bn254_g1_msm": (_i, [_vp, _sz, _sz, _vp, _sz, _vp, _sz, _vp]),
     "mi355zk_bn254_g2_msm": (_i, [_vp, _sz, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "mi355zk_bn254_g1_msm_strided": (_i, [_vp, _sz, _sz, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "mi355zk_bn254_g2_msm_strided": (_i, [_vp, _sz, _sz, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "mi355zk_bases_cache_pin_strided": (_i, [_vp, _sz, _sz, _sz, _sz, _sz, _i, _u32]),
+    "mi355zk_bn254_g1_records_pack_dev": (_i, [_vp, _sz, _sz, _sz, _sz, _sz, _vp, _vp]),
+    "mi355zk_bn254_g2_records_pack_dev": (_i, [_vp, _sz, _sz, _sz, _sz, _sz, _vp, _vp]),
     "mi355zk_bn254_g1_msm_dev": (_i, [_vp, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     "mi355zk_bn254_g2_msm_dev": (_i, [_vp, _sz, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     "mi355zk_bn254_g1_msm_part_dev": (_i, [_vp, _sz, _sz, _vp, _sz, _vp, _sz, _u32, _u32, _vp, _vp]),
