@@ -278,7 +278,11 @@ int mi355zk_bn254_fr_domain_op_batch_dev(void *const *d_arrays, uint32_t batch, 
 int mi355zk_bn254_fr_domain_constants(uint32_t log_n, uint64_t omega[4], uint64_t omegainv[4], uint64_t geninv[4], uint64_t minv[4]);
 
 /* ---- elementwise Fr operations of EvaluationDomain on device-resident data (asynchronous on `stream`):
- * a[i] *= b[i] (mul_assign, domain.rs:236-249) and a[i] -= b[i] (sub_assign, domain.rs:251-260). */
+ * a[i] *= b[i] (mul_assign, domain.rs:236-249) and a[i] -= b[i] (sub_assign, domain.rs:251-260).
+ * Operand range (these three entry points): every element is a Montgomery Fr as the reference holds one, i.e. a CANONICAL value < r on 4 x u64.
+ * The kernels do not check it.  For an element >= r the call still returns 0 and the element's result is UNDEFINED (not even congruent to the
+ * true product / difference in general: the product's reduction assumes a b < r 2^256, the difference one conditional correction); the results of
+ * the other elements are unaffected.  A caller with unreduced data reduces it first. */
 int mi355zk_bn254_fr_mul_assign_dev(void *d_a, const void *d_b, size_t n, void *stream);
 int mi355zk_bn254_fr_sub_assign_dev(void *d_a, const void *d_b, size_t n, void *stream);
 /* out[i] = into_repr(in[i]): Montgomery Fr -> canonical FrRepr (scalars_into_representations / field_elements_into_representations,
@@ -312,6 +316,31 @@ int mi355zk_selftest_glv2_split(const uint32_t k[8], uint32_t out[10]);
 int mi355zk_selftest_g2_psi(const uint64_t affine_pt[16], uint64_t out_xyz[24]);
 int mi355zk_selftest_g2_scalar_mul_u(const uint64_t affine_pt[16], const uint64_t scalar[4], uint64_t out_xyz[24]);
 int mi355zk_selftest_g2_accumulate(int mode, const uint64_t *affine_pts, const uint8_t *negate, size_t n, uint64_t out_xyzz[32]);
+
+/* ---- self-test hook ON THE DEVICE: one primitive of csrc/field.hpp / fieldu.hpp / curveu.hpp per lane, on operands the caller chose, so
+ * that the gfx950 object code -- and the code that exists in the device pass only: the Montgomery product of mont_mul_gfx950.inc, the quad-
+ * and pair-per-bucket additions -- meets hand-made edge operands (tests/field_edge_vectors.py).  Host buffers: case i is in[i * in_words_per_case ..],
+ * its result out[i * out_words_per_case ..]; the word counts are fixed per op (csrc/selftest_dev_ops.hpp: devop_shape) and a call with
+ * others, an unknown op, `which` == 1 (Fr) for an Fq-only op, or n_cases == 0 / not a multiple of the op's lane group returns rc 3.  One case
+ * per lane, 256 lanes per workgroup; the padding lanes repeat the last case.  The lane-group ops (_QUAD: 4 lanes, _PAIR_: 2) expect the SAME case
+ * in every lane of a group and return every lane's result.  op | MI355ZK_DEVOP_CHAIN runs the build of the op with ZK_CHAIN_MAD (fieldu.hpp),
+ * as msm_g1.hip and ntt.hip ship it: the U_ and G1_ ops only.  Field elements: 8 x 32-bit words (Fp), 9 x 29-bit limbs in u32 (U-form);
+ * a register-form point is X, Y, ZZ, ZZZ in U-form, a record the same four coordinates as canonical Fp words. */
+enum mi355zk_devop {
+  MI355ZK_DEVOP_FP_MUL = 0, MI355ZK_DEVOP_FP_SQR, MI355ZK_DEVOP_FP_ADD, MI355ZK_DEVOP_FP_SUB, MI355ZK_DEVOP_FP_DBL, MI355ZK_DEVOP_FP_NEG, MI355ZK_DEVOP_FP_REDUCE_ONCE, MI355ZK_DEVOP_FP_INV,
+  MI355ZK_DEVOP_FQ2_MUL, MI355ZK_DEVOP_FQ2_SQR, MI355ZK_DEVOP_FQ2_INV, MI355ZK_DEVOP_FQ2_ADD, MI355ZK_DEVOP_FQ2_SUB, MI355ZK_DEVOP_FQ2_NEG,
+  MI355ZK_DEVOP_U_FROM_STD, MI355ZK_DEVOP_U_CARRY, MI355ZK_DEVOP_U_TO_STD_LT2P, MI355ZK_DEVOP_U_TO_STD_LT32P, MI355ZK_DEVOP_U_ADD, MI355ZK_DEVOP_U_DBL,
+  MI355ZK_DEVOP_U_SUB_1_1, MI355ZK_DEVOP_U_SUB_2_1, MI355ZK_DEVOP_U_SUB_3_1, MI355ZK_DEVOP_U_SUB_4_1, MI355ZK_DEVOP_U_SUB_4_2, MI355ZK_DEVOP_U_SUB_4_3, MI355ZK_DEVOP_U_SUB_8_1, MI355ZK_DEVOP_U_SUB_16_1,
+  MI355ZK_DEVOP_U_MUL, MI355ZK_DEVOP_U_SQR, MI355ZK_DEVOP_U_MUL2, MI355ZK_DEVOP_U_MUL3, MI355ZK_DEVOP_U_MUL4, MI355ZK_DEVOP_U_MUL_SHOUP, MI355ZK_DEVOP_U_IS_ZERO_LT2P, MI355ZK_DEVOP_U_IS_ZERO_LT8P,
+  MI355ZK_DEVOP_F2U_MUL_2, MI355ZK_DEVOP_F2U_MUL_4, MI355ZK_DEVOP_F2U_MUL_8, MI355ZK_DEVOP_F2U_SQR_2, MI355ZK_DEVOP_F2U_SQR_4, MI355ZK_DEVOP_F2U_SQR_6, MI355ZK_DEVOP_F2U_SQR_8, MI355ZK_DEVOP_F2U_SUB_2, MI355ZK_DEVOP_F2U_SUB_3, MI355ZK_DEVOP_F2U_SUB_8,
+  MI355ZK_DEVOP_G1_DOUBLE_AFFINE, MI355ZK_DEVOP_G1_DOUBLE, MI355ZK_DEVOP_G1_ADD_MIXED, MI355ZK_DEVOP_G1_RADD, MI355ZK_DEVOP_G1_RECORD_TRIP, MI355ZK_DEVOP_G1_RADD_QUAD, MI355ZK_DEVOP_G1_PAIR_ADD_MIXED,
+  MI355ZK_DEVOP_G2_DOUBLE_AFFINE, MI355ZK_DEVOP_G2_DOUBLE, MI355ZK_DEVOP_G2_ADD_MIXED, MI355ZK_DEVOP_G2_RADD, MI355ZK_DEVOP_G2_RECORD_TRIP, MI355ZK_DEVOP_G2_RADD_QUAD, MI355ZK_DEVOP_G2_PAIR_ADD_MIXED,
+  MI355ZK_DEVOP_G1_JAC_DOUBLE, MI355ZK_DEVOP_G1_JAC_ADD_MIXED, MI355ZK_DEVOP_G1_JAC_ADD_TAB,
+  MI355ZK_DEVOP_G2_JAC_DOUBLE, MI355ZK_DEVOP_G2_JAC_ADD_TAB, MI355ZK_DEVOP_G2_JAC_TAB_PSI,
+  MI355ZK_DEVOP_COUNT
+};
+#define MI355ZK_DEVOP_CHAIN 0x100
+int mi355zk_selftest_dev_op(int op, int which, const uint32_t *in, size_t in_words_per_case, uint32_t *out, size_t out_words_per_case, size_t n_cases);
 
 /* ---- mode / flag bits of the scalar-multiplication entry points below (batch_exp: `mode`; point_fft: `mode`; sparse_matvec: `flags`).
  * batch_exp and sparse_matvec return, by default, the reference's result for EVERY record the reference's decoders admit (point_fft: for

@@ -255,7 +255,7 @@ ZK_HD Fp<PR> neg(const Fp<PR>& a) {
 // Montgomery product a*b*2^-256 mod p, fully reduced.
 //   device (gfx950): finely-integrated product scanning in inline asm (mont_mul_gfx950.inc, generated by
 //     tools/gen_mont_mul.py): per 32x32 partial product one v_mad_u64_u32 (64-bit accumulate) + one
-//     v_addc_co_u32 into the third accumulator word, no moves: 136 mad + 136 addc + 8 v_mul_lo_u32.
+//     v_addc_co_u32 into the third accumulator word, no moves: 128 mad + 128 addc + 8 v_mul_lo_u32.
 //   host: CIOS on 4 x 64-bit limbs with unsigned __int128 (portable 32-bit-limb CIOS kept as the fallback).
 template <class PR>
 ZK_HD Fp<PR> mul(const Fp<PR>& a, const Fp<PR>& b) {
