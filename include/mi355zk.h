@@ -292,6 +292,27 @@ int mi355zk_bn254_fr_into_repr_dev(void *d_out, const void *d_in, size_t n, void
  * generator (z(tau) = tau^m - 1, domain.rs:207-212) -- the division step of the prover's H polynomial (prover.rs:217-241), so that
  * the whole ifft / coset_fft / mul / sub / divide / icoset_fft pipeline stays in HBM.  Asynchronous on `stream`. */
 int mi355zk_bn254_fr_divide_by_z_on_coset_dev(void *d_a, uint32_t log_n, void *stream);
+/* The three elementwise steps of the H polynomial in ONE pass: a[i] = (a[i] * b[i] - c[i]) * zinv with zinv = (7^(2^log_n) - 1)^-1, i.e.
+ * mul_assign(a, b), sub_assign(a, c), divide_by_z_on_coset(a) (prover.rs:232-236), byte for byte, at three loads and one store per element
+ * instead of five loads and three stores.  n may be any length; log_n (<= 28) only selects z.  Operand range as for mul_assign / sub_assign
+ * above (canonical Montgomery Fr, unchecked).  d_a may not alias d_b or d_c.  Asynchronous on `stream`.  3 = a NULL pointer with n > 0, log_n > 28. */
+int mi355zk_bn254_fr_h_combine_dev(void *d_a, const void *d_b, const void *d_c, size_t n, uint32_t log_n, void *stream);
+/* The prover's H evaluation (prover.rs:216-248) on three DISTINCT device arrays of 2^log_n Montgomery Fr each: ifft and coset_fft of a, b, c
+ * (two mi355zk_bn254_fr_domain_op_batch_dev calls over the three), h_combine, icoset_fft of a and, with MI355ZK_H_INTO_REPR in
+ * `flags`, into_repr of every element.  On return (asynchronous on `stream`, no host synchronisation) d_a[0 .. 2^log_n) is what icoset_fft
+ * leaves -- the caller uses the first 2^log_n - 1 elements (prover.rs:243-246 drops the last coefficient) -- and d_b, d_c are SCRATCH: their
+ * contents are unspecified.  Byte-identical to the ten calls it replaces.  3 = a NULL or repeated pointer, log_n > 28, unknown flag bits. */
+#define MI355ZK_H_INTO_REPR 1u
+int mi355zk_bn254_fr_h_poly_dev(void *d_a, void *d_b, void *d_c, uint32_t log_n, uint32_t flags, void *stream);
+/* The same chain on HOST buffers, for a caller that holds `Vec<Scalar>`s (every Rust or C caller): a, b, c each hold `len` <= 2^log_n
+ * Montgomery Fr and are zero-padded to 2^log_n on the device, as EvaluationDomain::from_coeffs does (domain.rs:66-98); h receives the first
+ * 2^log_n - 1 elements of the result (none for log_n == 0, and the call still succeeds), canonical FrRepr with MI355ZK_H_INTO_REPR, else
+ * Montgomery.  128 B per element cross the link instead of the 448 B of seven mi355zk_bn254_fr_domain_op calls, the uploads in bounded
+ * pinned pieces that overlap the transforms of the array before.  Runs on the calling thread's current device; re-entrant from several host
+ * threads; device buffers and streams are leased from the library's pools.  a, b, c are never written.  Synchronous.
+ * 3 (before any device work) = a NULL pointer, log_n > 28, len == 0 or len > 2^log_n, unknown flag bits, h equal to a, b or c.
+ * On ANY non-zero return the contents of h are unspecified and a, b, c are intact: the caller can fall back to its CPU path. */
+int mi355zk_bn254_fr_h_poly(uint64_t *h, const uint64_t *a, const uint64_t *b, const uint64_t *c, size_t len, uint32_t log_n, uint32_t flags);
 /* EvaluationDomain::z (domain.rs:207-212): out = tau^(2^log_n) - 1, Montgomery in and out (host arithmetic). */
 int mi355zk_bn254_fr_domain_z(uint32_t log_n, const uint64_t tau[4], uint64_t out[4]);
 /* Measured Montgomery-product rate of this library (the integer-ALU roofline the kernels are priced

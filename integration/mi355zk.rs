@@ -40,6 +40,7 @@ pub const MI355ZK_FFT_INVERSE: c_int = 1; // point_fft `mode`: omega^-1 and the 
 pub const MI355ZK_G2_TRUSTED_SUBGROUP: c_int = 2; // batch_exp / point_fft / sparse_matvec: the caller's promise
 pub const MI355ZK_NO_FLAG: usize = usize::MAX; // msm_strided / pin_strided `inf_off`: the records carry no infinity flag
 pub const MI355ZK_PIN_TABLES: u32 = 1; // pin_strided `flags`: keep the window table too
+pub const MI355ZK_H_INTO_REPR: u32 = 1; // fr_h_poly[_dev] `flags`: the result as canonical FrRepr (scalars_into_representations fused)
 
 // ---- BEGIN GENERATED (tools/gen_rust_ffi.py from include/mi355zk.h) ----
 #[link(name = "mi355zk")]
@@ -98,6 +99,9 @@ extern "C" {
     pub fn mi355zk_bn254_fr_sub_assign_dev(d_a: *mut c_void, d_b: *const c_void, n: usize, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_fr_into_repr_dev(d_out: *mut c_void, d_in: *const c_void, n: usize, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_fr_divide_by_z_on_coset_dev(d_a: *mut c_void, log_n: u32, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_bn254_fr_h_combine_dev(d_a: *mut c_void, d_b: *const c_void, d_c: *const c_void, n: usize, log_n: u32, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_bn254_fr_h_poly_dev(d_a: *mut c_void, d_b: *mut c_void, d_c: *mut c_void, log_n: u32, flags: u32, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_bn254_fr_h_poly(h: *mut u64, a: *const u64, b: *const u64, c: *const u64, len: usize, log_n: u32, flags: u32) -> c_int;
     pub fn mi355zk_bn254_fr_domain_z(log_n: u32, tau: *const u64 /* [4] */, out: *mut u64 /* [4] */) -> c_int;
     pub fn mi355zk_bn254_g1_sparse_matvec_dev(d_out_affine: *mut c_void, d_bases_affine: *const c_void, n_bases: usize, d_row_ptr: *const u32, d_col: *const u32, d_coeffs: *const c_void, n_rows: usize, nnz: usize, stream: *mut c_void, flags: c_int) -> c_int;
     pub fn mi355zk_bn254_g2_sparse_matvec_dev(d_out_affine: *mut c_void, d_bases_affine: *const c_void, n_bases: usize, d_row_ptr: *const u32, d_col: *const u32, d_coeffs: *const c_void, n_rows: usize, nnz: usize, stream: *mut c_void, flags: c_int) -> c_int;
@@ -382,6 +386,36 @@ pub fn try_best_fft<E: Engine, T: Group<E>>(a: &mut [T], omega: &E::Fr, log_n: u
         return false;
     }
     unsafe { mi355zk_bn254_fr_ntt(a.as_mut_ptr() as *mut u64, log_n, omega as *const E::Fr as *const u64) == 0 }
+}
+
+/// The H evaluation of `create_proof` (prover.rs:216-248) for `T = Scalar<Bn256>` in one call: a, b and c are the prover's three
+/// evaluation vectors as they come out of `ProvingAssignment` (one length, Montgomery limbs); the library pads them to the domain size
+/// as `EvaluationDomain::from_coeffs` does (domain.rs:66-98), runs ifft / coset_fft / a * b - c / divide_by_z_on_coset / icoset_fft in
+/// HBM and returns the first 2^log_n - 1 coefficients already `into_repr()`ed -- the `Arc<Vec<FrRepr>>` the h multiexp takes.  a, b and c
+/// are only read.  `None` on ANY non-zero return code (another engine, a device failure, arguments the library refuses): the caller then
+/// runs its own `EvaluationDomain` chain on the untouched vectors, so a broken GPU never changes a proof.
+pub fn try_h_poly<E: Engine, T: Group<E>>(a: &[T], b: &[T], c: &[T]) -> Option<Vec<<E::Fr as PrimeField>::Repr>> {
+    if TypeId::of::<E>() != TypeId::of::<Bn256>() || mem::size_of::<T>() != 32 || mem::size_of::<<E::Fr as PrimeField>::Repr>() != 32 {
+        return None;
+    }
+    if a.is_empty() || b.len() != a.len() || c.len() != a.len() || !abi_ok() {
+        return None;
+    }
+    let mut log_n = 0u32; // from_coeffs: the smallest power of two >= len (domain.rs:70-79)
+    while (1usize << log_n) < a.len() {
+        log_n += 1;
+        if log_n > 28 {
+            return None; // PolynomialDegreeTooLarge: the CPU path reports it
+        }
+    }
+    let mut h = vec![<E::Fr as PrimeField>::Repr::default(); (1usize << log_n) - 1];
+    let mut none = [0u64; 4]; // (log_n == 0: nothing is written, but the entry takes no NULL)
+    let hp = if h.is_empty() { none.as_mut_ptr() } else { h.as_mut_ptr() as *mut u64 };
+    let rc = unsafe { mi355zk_bn254_fr_h_poly(hp, a.as_ptr() as *const u64, b.as_ptr() as *const u64, c.as_ptr() as *const u64, a.len(), log_n, MI355ZK_H_INTO_REPR) };
+    if rc != 0 {
+        return None;
+    }
+    Some(h)
 }
 
 /// Once per process, e.g. from `Worker::new()` (multicore.rs:24-35): every visible GPU becomes part of the device set, and host-buffer

@@ -21,6 +21,7 @@ from .bellman import (  # noqa: F401
     StridedBases,
     SynthesisError,
     Worker,
+    h_poly_host,
     multiexp,
     pin_bases,
     unpin_bases,

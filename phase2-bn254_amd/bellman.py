@@ -465,6 +465,46 @@ class EvaluationDomain:
         if rc != 0:
             raise DeviceError(f"mi355zk sub_assign failed rc={rc}")
 
+    @staticmethod
+    def h_poly(a: "EvaluationDomain", b: "EvaluationDomain", c: "EvaluationDomain", worker: Worker, into_repr: bool = False) -> "EvaluationDomain":
+        """The prover's H evaluation (prover.rs:216-248) on three device-resident domains of one size, in ONE library call
+        (mi355zk_bn254_fr_h_poly_dev): ifft and coset_fft of a, b, c, a = (a * b - c) / z in one elementwise pass, icoset_fft and, with
+        into_repr, the conversion to canonical FrRepr.  Returns `a`, whose coefficients hold the result -- the caller drops the last one
+        (prover.rs:243-246); b and c are scratch afterwards.  Byte for byte what the ten separate calls leave."""
+        ta, tb, tc = a.coeffs, b.coeffs, c.coeffs
+        if not all(_is_torch(t) and t.is_cuda and t.is_contiguous() for t in (ta, tb, tc)):
+            raise ValueError("device-resident coefficients (contiguous torch CUDA tensors) required")
+        assert a.exp == b.exp == c.exp and ta.shape[0] == tb.shape[0] == tc.shape[0] == 1 << a.exp
+        assert ta.device == tb.device == tc.device
+        with a._on_device():
+            rc = _lib.load().mi355zk_bn254_fr_h_poly_dev(C.c_void_p(ta.data_ptr()), C.c_void_p(tb.data_ptr()), C.c_void_p(tc.data_ptr()), a.exp,
+                                                         _lib.H_INTO_REPR if into_repr else 0, _stream_ptr())
+        if rc == _lib.ERR_BAD_ARGS:
+            raise ValueError("mi355zk_bn254_fr_h_poly_dev: bad arguments")
+        if rc != 0:
+            raise DeviceError(f"mi355zk h_poly failed rc={rc}")
+        return a
+
+
+def h_poly_host(a, b, c, log_n: int, into_repr: bool = False):
+    """The same chain on HOST arrays (mi355zk_bn254_fr_h_poly): a, b, c are (len, 4) u64 Montgomery Fr with len <= 2^log_n, zero-padded
+    by the library as `from_coeffs` does; returns the (2^log_n - 1, 4) coefficients of h (canonical FrRepr with into_repr).  One upload
+    of the three arrays and one download, instead of seven round trips through mi355zk_bn254_fr_domain_op.  The inputs are not written."""
+    arrs = [np.ascontiguousarray(x, dtype=np.uint64) for x in (a, b, c)]
+    if not all(x.ndim == 2 and x.shape[1] == 4 and x.shape[0] == arrs[0].shape[0] for x in arrs):
+        raise ValueError("a, b, c: three (len, 4) u64 arrays of one length")
+    if not 0 <= log_n <= FR_S:
+        raise SynthesisError(SynthesisError.POLYNOMIAL_DEGREE_TOO_LARGE)
+    h = np.empty(((1 << log_n) - 1, 4), dtype=np.uint64)
+    hp = h.ctypes.data_as(C.c_void_p) if h.size else np.empty((1, 4), dtype=np.uint64).ctypes.data_as(C.c_void_p)
+    rc = _lib.load().mi355zk_bn254_fr_h_poly(hp, *[x.ctypes.data_as(C.c_void_p) for x in arrs], arrs[0].shape[0], log_n,
+                                             _lib.H_INTO_REPR if into_repr else 0)
+    if rc == _lib.ERR_BAD_ARGS:
+        raise ValueError("mi355zk_bn254_fr_h_poly: bad arguments")
+    if rc != 0:
+        raise DeviceError(f"mi355zk h_poly failed rc={rc}")
+    return h
+
 
 def best_fft(a, worker: Worker, omega, log_n: int):
     """bellman/src/domain.rs:263: in-place transform of `a` (numpy (2^log_n, 4) u64) with root `omega`."""

@@ -198,6 +198,13 @@ int domain_consts(uint32_t exp, DomainConsts* d) {
   d->minv = inv(fr_from_u64(1ull << exp));
   return ZK_OK;
 }
+
+// 1 / z on the coset: (g^m - 1)^-1 with m = 2^log_n, g = 7 (divide_by_z_on_coset, domain.rs:217-234)
+Fr domain_zinv(uint32_t log_n) {
+  Fr z = fr_from_u64(7);                             // E::Fr::multiplicative_generator() (fr.rs:5)
+  for (uint32_t i = 0; i < log_n; ++i) z = sqr(z);
+  return inv(sub(z, Fr::one()));
+}
 }  // namespace
 
 int domain_op_dev(Fr* d_a, uint32_t log_n, int op, hipStream_t st) {
@@ -238,6 +245,16 @@ int domain_op_batch_dev(Fr* const* d_arrays, uint32_t batch, uint32_t log_n, int
     if (rc) return rc;
   }
   return ZK_OK;
+}
+
+
+int h_poly_finish_dev(Fr* d_a, const Fr* d_b, const Fr* d_c, uint32_t log_n, uint32_t flags, hipStream_t st) {
+  const size_t n = (size_t)1 << log_n;
+  int rc = fr_h_combine(d_a, d_b, d_c, n, domain_zinv(log_n), st);
+  if (rc) return rc;
+  rc = domain_op_dev(d_a, log_n, MI355ZK_OP_ICOSET_FFT, st);
+  if (rc) return rc;
+  return (flags & MI355ZK_H_INTO_REPR) ? fr_into_repr(d_a, d_a, n, st) : ZK_OK;
 }
 
 }  // namespace zk
@@ -620,10 +637,34 @@ int mi355zk_bn254_fr_domain_z(uint32_t log_n, const uint64_t tau[4], uint64_t ou
 int mi355zk_bn254_fr_divide_by_z_on_coset_dev(void* d_a, uint32_t log_n, void* stream) {
   return abi_guard([&]() -> int {
     if (!d_a || log_n > 28) return ZK_ERR_BAD_ARGS;
-    Fr z = fr_from_u64(7);                             // E::Fr::multiplicative_generator() (fr.rs:5)
-    for (uint32_t i = 0; i < log_n; ++i) z = sqr(z);
-    z = sub(z, Fr::one());
-    return ntt_scale((Fr*)d_a, log_n, inv(z), nullptr, (hipStream_t)stream);
+    return ntt_scale((Fr*)d_a, log_n, domain_zinv(log_n), nullptr, (hipStream_t)stream);
+  });
+}
+// the three elementwise steps of the H polynomial in one pass (field_ops.hip: fr_h_combine_kernel)
+int mi355zk_bn254_fr_h_combine_dev(void* d_a, const void* d_b, const void* d_c, size_t n, uint32_t log_n, void* stream) {
+  return abi_guard([&]() -> int {
+    if (log_n > 28 || (n && (!d_a || !d_b || !d_c))) return ZK_ERR_BAD_ARGS;
+    if (n == 0) return ZK_OK;
+    return fr_h_combine((Fr*)d_a, (const Fr*)d_b, (const Fr*)d_c, n, domain_zinv(log_n), (hipStream_t)stream);
+  });
+}
+// prover.rs:216-248 on device arrays: ifft and coset_fft of a, b, c (batched), combine, icoset_fft, into_repr
+int mi355zk_bn254_fr_h_poly_dev(void* d_a, void* d_b, void* d_c, uint32_t log_n, uint32_t flags, void* stream) {
+  return abi_guard([&]() -> int {
+    if (!d_a || !d_b || !d_c || d_a == d_b || d_a == d_c || d_b == d_c || log_n > 28 || (flags & ~MI355ZK_H_INTO_REPR)) return ZK_ERR_BAD_ARGS;
+    Fr* const arrays[3] = {(Fr*)d_a, (Fr*)d_b, (Fr*)d_c};
+    int rc = domain_op_batch_dev(arrays, 3, log_n, MI355ZK_OP_IFFT, (hipStream_t)stream);
+    if (rc) return rc;
+    rc = domain_op_batch_dev(arrays, 3, log_n, MI355ZK_OP_COSET_FFT, (hipStream_t)stream);
+    if (rc) return rc;
+    return h_poly_finish_dev(arrays[0], arrays[1], arrays[2], log_n, flags, (hipStream_t)stream);
+  });
+}
+int mi355zk_bn254_fr_h_poly(uint64_t* h, const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t len, uint32_t log_n, uint32_t flags) {
+  return abi_guard([&]() -> int {
+    if (!h || !a || !b || !c || log_n > 28 || (flags & ~MI355ZK_H_INTO_REPR)) return ZK_ERR_BAD_ARGS;
+    if (len == 0 || len > ((size_t)1 << log_n) || h == a || h == b || h == c) return ZK_ERR_BAD_ARGS;
+    return h_poly_host(h, a, b, c, len, log_n, flags);
   });
 }
 

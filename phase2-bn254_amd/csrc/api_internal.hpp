@@ -82,8 +82,15 @@ int records_layout_check(int group, size_t stride, size_t x_off, size_t y_off, s
 // n raw records at d_raw -> n packed records at d_out (the records_pack kernel, enqueued on `st`; no synchronisation)
 int records_pack_run(int group, const void* d_raw, size_t n, const RecordLayout& L, void* d_out, hipStream_t st);
 
+// field_ops.hip
+int fr_h_combine(Fr* d_a, const Fr* d_b, const Fr* d_c, size_t n, const Fr& zinv, hipStream_t st);   // a[i] = (a[i] * b[i] - c[i]) * zinv, one pass
+int fr_into_repr(Fr* d_out, const Fr* d_in, size_t n, hipStream_t st);                                // Montgomery -> canonical (d_out may alias d_in)
+
 // api.hip
 int domain_op_dev(Fr* d_a, uint32_t log_n, int op, hipStream_t st);   // EvaluationDomain::{fft, ifft, coset_fft, icoset_fft} on a device array
+int domain_op_batch_dev(Fr* const* d_arrays, uint32_t batch, uint32_t log_n, int op, hipStream_t st);
+// the H polynomial of prover.rs:216-248 behind a, b, c in the coset evaluation form: h_combine, icoset_fft, into_repr (MI355ZK_H_INTO_REPR)
+int h_poly_finish_dev(Fr* d_a, const Fr* d_b, const Fr* d_c, uint32_t log_n, uint32_t flags, hipStream_t st);
 
 // host_entry.hip
 struct DeviceGuard {  // the calling thread's current device is its own business: restore it
@@ -106,6 +113,7 @@ int batch_exp_host(uint8_t* out, const uint8_t* bases, const uint64_t* scalars, 
 template <int GROUP>
 int dense_host(const uint8_t* v1, const uint8_t* v2, const uint64_t* rho, size_t n, uint64_t* out_s, uint64_t* out_sx);
 int ntt_host(uint64_t* a, uint32_t log_n, int op, const uint64_t* omega);
+int h_poly_host(uint64_t* h, const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t len, uint32_t log_n, uint32_t flags);
 template <class F>
 int sparse_matvec(void* d_out, const void* d_bases, size_t n_bases, const uint32_t* d_row_ptr, const uint32_t* d_col, const void* d_coeffs,
                   size_t n_rows, size_t nnz, void* stream, int group, bool g2_trusted, void* d_scratch = nullptr, size_t scratch_bytes = 0);

@@ -39,6 +39,16 @@ __global__ void __launch_bounds__(256) fr_pointwise_kernel(Fr* __restrict__ a, c
   }
 }
 
+// a[i] = (a[i] * b[i] - c[i]) * zinv: mul_assign, sub_assign and divide_by_z_on_coset of the prover's H polynomial (prover.rs:232-236) in one
+// pass -- three 32-byte loads and one store per element (128 B) where the three passes move 256 B.  Every step returns the canonical
+// residue, as the separate kernels do, so the result is theirs byte for byte.
+__global__ void __launch_bounds__(256) fr_h_combine_kernel(Fr* __restrict__ a, const Fr* __restrict__ b, const Fr* __restrict__ c, uint64_t n, Fr zinv) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const Fr x = ld(a + i), y = ld(b + i), z = ld(c + i);
+    st(a + i, mul(sub(mul(x, y), z), zinv));
+  }
+}
+
 // out[i] = into_repr(in[i]): Montgomery form -> canonical integer (one Montgomery reduction; out may alias in)
 __global__ void __launch_bounds__(256) fr_into_repr_kernel(Fr* out, const Fr* in, uint64_t n) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
@@ -101,6 +111,23 @@ int pointwise(void* d_a, const void* d_b, size_t n, void* stream, int op) {
 }
 
 }  // namespace
+
+int fr_h_combine(Fr* d_a, const Fr* d_b, const Fr* d_c, size_t n, const Fr& zinv, hipStream_t st) {
+  if (n == 0) return ZK_OK;
+  uint64_t blocks = (n + 255) / 256;
+  if (blocks > 16384) blocks = 16384;
+  hipLaunchKernelGGL(fr_h_combine_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_a, d_b, d_c, (uint64_t)n, zinv);
+  ZK_HIP(hipGetLastError());
+  return ZK_OK;
+}
+int fr_into_repr(Fr* d_out, const Fr* d_in, size_t n, hipStream_t st) {
+  if (n == 0) return ZK_OK;
+  uint64_t blocks = (n + 255) / 256;
+  if (blocks > 16384) blocks = 16384;
+  hipLaunchKernelGGL(fr_into_repr_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_out, d_in, (uint64_t)n);
+  ZK_HIP(hipGetLastError());
+  return ZK_OK;
+}
 }  // namespace zk
 
 // ---- host-side self-test hooks for the U-form arithmetic (same source as the kernels, compiled for the host)
@@ -492,12 +519,7 @@ int mi355zk_bn254_fr_sub_assign_dev(void* d_a, const void* d_b, size_t n, void* 
 int mi355zk_bn254_fr_into_repr_dev(void* d_out, const void* d_in, size_t n, void* stream) {
   return zk::abi_guard([&]() -> int {
     if ((!d_out || !d_in) && n) return ZK_ERR_BAD_ARGS;
-    if (n == 0) return ZK_OK;
-    uint64_t blocks = (n + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(zk::fr_into_repr_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (zk::Fr*)d_out, (const zk::Fr*)d_in, (uint64_t)n);
-    ZK_HIP(hipGetLastError());
-    return ZK_OK;
+    return zk::fr_into_repr((zk::Fr*)d_out, (const zk::Fr*)d_in, n, (hipStream_t)stream);
   });
 }
 

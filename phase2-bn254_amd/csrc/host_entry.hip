@@ -1171,6 +1171,69 @@ int ntt_host(uint64_t* a, uint32_t log_n, int op, const uint64_t* omega) {
   return ZK_OK;
 }
 
+// The prover's H polynomial (prover.rs:216-248) from three HOST arrays: one upload of a, b and c, the chain in HBM, one download of
+// h -- 128 B per element over the link where seven ntt_host calls move 448 B.  The arrays travel one after the other on the copy
+// stream, in pieces of H_POLY_PIECE elements (what the runtime's pinned staging holds per hop -- the streamed multiexp's uploads go
+// the same way), and an array's ifft and coset_fft are queued on the compute stream behind the event that ends its upload: they run
+// while the next array crosses the link, so that only c's two transforms, the combine and the icoset_fft are exposed behind the last
+// byte.  (Pipelined single transforms rather than the batched launches of the device entry behind the last upload: measured on one box,
+// profiles/h_poly.md -- 2^20 3.14-3.28 ms against 3.52-3.54 ms; 2^16 0.40-0.45 against 0.37-0.39, inside that size's run-to-run spread.)
+// The inputs are only read; h is written by the
+// final copy only.  Buffer, streams: the pools of the host-buffer entry points; three events per call, as msm_host_run makes its own.
+constexpr size_t H_POLY_PIECE = (size_t)1 << 17;   // elements per copy (4 MiB)
+int h_poly_host(uint64_t* h, const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t len, uint32_t log_n, uint32_t flags) {
+  const size_t n = (size_t)1 << log_n, bytes = n * 32;
+  int dev = 0;
+  ZK_HIP(hipGetDevice(&dev));
+  StageLease stage_lease;
+  HostStage* S = host_stage(dev, &stage_lease);
+  if (S == nullptr) return ZK_ERR_DEVICE;
+  DensityPool::Lease buf;
+  int rc = buf.acquire(dev, 3 * bytes, S->compute);
+  if (rc) return rc;
+  struct Events {
+    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    HostStage* S;
+    ~Events() {
+      // an error path may leave copies queued into the leased buffer: both streams are idle before it goes back to the pool
+      (void)hipStreamSynchronize(S->copy);
+      (void)hipStreamSynchronize(S->compute);
+      for (hipEvent_t x : e)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } ev;
+  ev.S = S;
+  for (hipEvent_t& x : ev.e) ZK_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming));
+  Fr* d[3] = {(Fr*)buf.b->p, (Fr*)buf.b->p + n, (Fr*)buf.b->p + 2 * n};
+  const uint64_t* src[3] = {a, b, c};
+  for (int k = 0; k < 3; ++k) {
+    if (len < n) ZK_HIP(hipMemsetAsync(d[k] + len, 0, (n - len) * 32, S->copy));   // from_coeffs: resize(m, zero) (domain.rs:80-82)
+    for (size_t lo = 0; lo < len; lo += H_POLY_PIECE) {
+      const size_t m = len - lo < H_POLY_PIECE ? len - lo : H_POLY_PIECE;
+      ZK_HIP(hipMemcpyAsync(d[k] + lo, src[k] + lo * 4, m * 32, hipMemcpyHostToDevice, S->copy));
+    }
+    ZK_HIP(hipEventRecord(ev.e[k], S->copy));
+    ZK_HIP(hipStreamWaitEvent(S->compute, ev.e[k], 0));
+#ifndef ZK_H_POLY_HOST_BATCHED
+    rc = domain_op_dev(d[k], log_n, MI355ZK_OP_IFFT, S->compute);
+    if (rc == ZK_OK) rc = domain_op_dev(d[k], log_n, MI355ZK_OP_COSET_FFT, S->compute);
+    if (rc != ZK_OK) return rc;
+#endif
+  }
+#ifdef ZK_H_POLY_HOST_BATCHED   // (the variant the pipelined form was measured against: tools/build_variant.sh, profiles/h_poly.md)
+  rc = domain_op_batch_dev(d, 3, log_n, MI355ZK_OP_IFFT, S->compute);
+  if (rc == ZK_OK) rc = domain_op_batch_dev(d, 3, log_n, MI355ZK_OP_COSET_FFT, S->compute);
+  if (rc != ZK_OK) return rc;
+#endif
+  rc = h_poly_finish_dev(d[0], d[1], d[2], log_n, flags, S->compute);
+  if (rc != ZK_OK) return rc;
+  ZK_HIP(hipStreamSynchronize(S->compute));  // a failed kernel surfaces here
+  if (n > 1) {
+    ZK_HIP(hipMemcpyAsync(h, d[0], (n - 1) * 32, hipMemcpyDeviceToHost, S->compute));   // the last coefficient is dropped (prover.rs:243-246)
+    ZK_HIP(hipStreamSynchronize(S->compute));
+  }
+  return ZK_OK;
+}
 
 
 // out[r] = sum_{t in [row_ptr[r], row_ptr[r+1])} coeff[t] * bases[col[t]], affine (QAP evaluation, parameters.rs:225-294)

@@ -167,6 +167,28 @@ class EvaluationDomain {
     if (other.coeffs_.size() != coeffs_.size()) throw std::logic_error("assertion failed: self.coeffs.len() == other.coeffs.len()");
     pointwise(other, mi355zk_bn254_fr_sub_assign_dev);
   }
+  // The prover's H evaluation (prover.rs:216-248) in ONE device call (mi355zk_bn254_fr_h_poly_dev): ifft and coset_fft of a, b and c,
+  // a = (a * b - c) / z, icoset_fft and, with into_repr, scalars_into_representations.  a receives all 2^exp coefficients (the caller
+  // drops the last one, prover.rs:243-246); b and c are only read (their device copies are the call's scratch).  One upload of the three
+  // vectors and one download where the ten separate members above make ten round trips.
+  static void h_poly(EvaluationDomain& a, const EvaluationDomain& b, const EvaluationDomain& c, const Worker&, bool into_repr = false) {
+    const size_t bytes = a.coeffs_.size() * 32;
+    if (b.coeffs_.size() != a.coeffs_.size() || c.coeffs_.size() != a.coeffs_.size() || b.exp_ != a.exp_ || c.exp_ != a.exp_)
+      throw std::logic_error("assertion failed: a, b and c are domains of one size");
+    void* d[3] = {nullptr, nullptr, nullptr};
+    const EvaluationDomain* src[3] = {&a, &b, &c};
+    int rc = 0;
+    for (int k = 0; k < 3 && rc == 0; ++k) {
+      rc = mi355zk_malloc(&d[k], bytes);
+      if (rc == 0) rc = mi355zk_memcpy_h2d(d[k], src[k]->coeffs_.data(), bytes);
+    }
+    if (rc == 0) rc = mi355zk_bn254_fr_h_poly_dev(d[0], d[1], d[2], a.exp_, into_repr ? MI355ZK_H_INTO_REPR : 0u, nullptr);
+    if (rc == 0) rc = mi355zk_sync(nullptr);
+    if (rc == 0) rc = mi355zk_memcpy_d2h(a.coeffs_.data(), d[0], bytes);
+    for (void* p : d)
+      if (p) (void)mi355zk_free(p);
+    if (rc != 0) throw SynthesisError(SynthesisError::Device);
+  }
   // scalars_into_representations (prover.rs:110-129): Montgomery -> canonical, on the device
   std::vector<FrRepr> into_representations() const {
     std::vector<FrRepr> out(coeffs_.size());
@@ -212,5 +234,20 @@ class EvaluationDomain {
   std::vector<Fr> coeffs_;
   uint32_t exp_ = 0;
 };
+
+// The same chain from HOST vectors through the host-buffer entry (mi355zk_bn254_fr_h_poly): a, b and c hold len <= 2^log_n Montgomery
+// elements each and are zero-padded by the library as from_coeffs does; returns the 2^log_n - 1 coefficients of h (canonical FrRepr
+// with into_repr).  The library leases its device buffers and overlaps the uploads with the transforms; the inputs are not written.
+inline std::vector<Fr> h_poly_host(const std::vector<Fr>& a, const std::vector<Fr>& b, const std::vector<Fr>& c, uint32_t log_n, bool into_repr = false) {
+  if (b.size() != a.size() || c.size() != a.size()) throw std::logic_error("assertion failed: a, b and c have one length");
+  if (log_n > EvaluationDomain::FR_S) throw SynthesisError(SynthesisError::PolynomialDegreeTooLarge);
+  std::vector<Fr> h(((size_t)1 << log_n) - 1);
+  Fr none{};   // (log_n == 0: nothing is written, but the entry takes no NULL)
+  int rc = mi355zk_bn254_fr_h_poly(h.empty() ? none.data() : h[0].data(), a.empty() ? nullptr : a[0].data(), b.empty() ? nullptr : b[0].data(),
+                                   c.empty() ? nullptr : c[0].data(), a.size(), log_n, into_repr ? MI355ZK_H_INTO_REPR : 0u);
+  if (rc == MI355ZK_ERR_BAD_ARGS) throw std::logic_error("mi355zk_bn254_fr_h_poly: bad arguments");
+  if (rc != 0) throw SynthesisError(SynthesisError::Device);
+  return h;
+}
 
 }  // namespace bellman

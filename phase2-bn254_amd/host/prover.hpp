@@ -132,17 +132,8 @@ inline Proof create_proof(const Worker& worker, const Parameters& params, Provin
     EvaluationDomain a = EvaluationDomain::from_coeffs(std::move(prover.a));
     EvaluationDomain b = EvaluationDomain::from_coeffs(std::move(prover.b));
     EvaluationDomain c = EvaluationDomain::from_coeffs(std::move(prover.c));
-    a.ifft(worker);
-    a.coset_fft(worker);
-    b.ifft(worker);
-    b.coset_fft(worker);
-    c.ifft(worker);
-    c.coset_fft(worker);
-    a.mul_assign(worker, b);
-    a.sub_assign(worker, c);
-    a.divide_by_z_on_coset(worker);
-    a.icoset_fft(worker);
-    std::vector<FrRepr> repr = a.into_representations();   // scalars_into_representations (prover.rs:110-129)
+    EvaluationDomain::h_poly(a, b, c, worker, /*into_repr=*/true);   // prover.rs:220-241 + scalars_into_representations (prover.rs:110-129), one device call
+    std::vector<FrRepr> repr = std::move(a).into_coeffs();
     repr.resize(repr.size() - 1);                           // a.truncate(a_len)
     h_repr = std::make_shared<const std::vector<FrRepr>>(std::move(repr));
   }

@@ -17,6 +17,7 @@ OP_FFT, OP_IFFT, OP_COSET_FFT, OP_ICOSET_FFT = 0, 1, 2, 3
 MSM_SCALARS_MONTGOMERY = 1
 NO_FLAG, PIN_TABLES = (1 << 64) - 1, 1   # MI355ZK_NO_FLAG (inf_off: no infinity flag byte) / MI355ZK_PIN_TABLES (include/mi355zk.h)
 ABI_VERSION = 7   # MI355ZK_ABI_VERSION of the include/mi355zk.h this table was written against: load() refuses another library
+H_INTO_REPR = 1   # MI355ZK_H_INTO_REPR: flags of fr_h_poly[_dev]
 EXP_SAME_SCALAR, FFT_INVERSE, G2_TRUSTED_SUBGROUP = 1, 1, 2   # mode / flag bits of batch_exp, point_fft, sparse_matvec (include/mi355zk.h)
 
 _vp, _sz, _i, _u32 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32
@@ -78,6 +79,9 @@ SIGNATURES = {
     "mi355zk_bn254_fr_sub_assign_dev": (_i, [_vp, _vp, _sz, _vp]),
     "mi355zk_bn254_fr_into_repr_dev": (_i, [_vp, _vp, _sz, _vp]),
     "mi355zk_bn254_fr_divide_by_z_on_coset_dev": (_i, [_vp, _u32, _vp]),
+    "mi355zk_bn254_fr_h_combine_dev": (_i, [_vp, _vp, _vp, _sz, _u32, _vp]),
+    "mi355zk_bn254_fr_h_poly_dev": (_i, [_vp, _vp, _vp, _u32, _u32, _vp]),
+    "mi355zk_bn254_fr_h_poly": (_i, [_vp, _vp, _vp, _vp, _sz, _u32, _u32]),
     "mi355zk_bn254_fr_domain_z": (_i, [_u32, _vp, _vp]),
     "mi355zk_ubench_fp_mul": (_i, [_i, _u32, _u32, _vp, _vp, _vp, C.POINTER(C.c_float)]),
     "mi355zk_selftest_g1_record_sum": (_i, [_i, _vp, _vp, _vp, _sz, _sz, _vp]),

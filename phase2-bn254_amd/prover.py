@@ -181,16 +181,10 @@ def create_proof(pool: Worker, params: Parameters, prover: ProvingAssignment, r:
     a = EvaluationDomain.from_coeffs(prover.a)
     b = EvaluationDomain.from_coeffs(prover.b)
     c = EvaluationDomain.from_coeffs(prover.c)
-    # (prover.rs:220-231 transforms a, b and c one after the other; the three are independent, and one launch per pass over all three lets
-    # one transform's loads and stores run under another's butterflies -- same bytes)
-    EvaluationDomain.ifft_many(pool, (a, b, c))
-    EvaluationDomain.coset_fft_many(pool, (a, b, c))
-    a.mul_assign(pool, b)
-    del b
-    a.sub_assign(pool, c)
-    del c
-    a.divide_by_z_on_coset(pool)
-    a.icoset_fft(pool)
+    # (prover.rs:220-241 as ONE library call: the transforms of a, b and c batched -- one launch per pass over all three, same bytes --
+    # a = (a * b - c) / z in one elementwise pass, icoset_fft.  The coefficients stay Montgomery forms: the multiexp converts them.)
+    EvaluationDomain.h_poly(a, b, c, pool)
+    del b, c
     coeffs = a.into_coeffs()
     coeffs = coeffs[:coeffs.shape[0] - 1]                       # a.truncate(a_len)
     # the multiexp threads use their own streams: the H pipeline (queued on the stream of the TENSORS' device, which need not be
