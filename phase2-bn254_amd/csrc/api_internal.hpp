@@ -1,5 +1,6 @@
 // Internal interfaces between the translation units of libmi355zk.so (not part of the C ABI: include/mi355zk.h is).
 //   api.hip         the C ABI: argument checking, domain constants, device-resident entry points, profiling hooks, lifecycle
+//   host_entry.hip  the host-buffer entry points: Source / Density plan, bases cache, streamed upload, multi-GPU cells
 //   scalar_mul.hip  the scalar-multiplication kernels and their launchers: batch_exp / batch_mul / window-table build / G2 membership
 //   (msm_g1.hip, msm_g2.hip, ntt.hip, point_fft*.hip, codec.hip, field_ops.hip, records.hip: the kernels behind the functions declared below)
 #pragma once
@@ -20,7 +21,7 @@ int ntt_run_batch(Fr* const* d_arrays, uint32_t batch, uint32_t log_n, const Fr&
 int ntt_scale(Fr* d_a, uint32_t log_n, const Fr& c, const Fr* g, hipStream_t st);
 void ntt_release_all();
 int ntt_configure();
-// msm.hip
+// msm_g1.hip, msm_g2.hip (the kernels and msm_device: msm_impl.hpp)
 int msm_g1_device(const void* d_bases, uint64_t n_bases, uint64_t base_offset, const void* d_scalars, uint64_t n, const uint32_t* d_density,
                   const uint32_t* d_dprefix, hipStream_t st, uint64_t out_xyz[12], long long* err_index, uint32_t wgroups, uint32_t wgroup, bool scalars_mont,
                   MsmChunks* chunks, uint64_t table_stride = 0, uint32_t table_c = 0);
@@ -30,13 +31,6 @@ int msm_g2_device(const void* d_bases, uint64_t n_bases, uint64_t base_offset, c
                   MsmChunks* chunks, uint64_t table_stride = 0, uint32_t table_c = 0);
 int msm_g1_dense_device(const void* d_bases, const void* d_bases2, const void* d_scalars, uint64_t n, hipStream_t st, uint64_t* out_xyz, uint64_t* out2_xyz);
 int msm_g2_dense_device(const void* d_bases, const void* d_bases2, const void* d_scalars, uint64_t n, hipStream_t st, uint64_t* out_xyz, uint64_t* out2_xyz);
-// point_fft.hip
-int point_fft_g1(void* d_points, uint32_t log_n, const Fr& omega, bool scale, const Fr& scale_canon, hipStream_t st);
-// codec.hip
-int codec_decode(int group, void* d_out, const void* d_in, size_t n, int compressed, int checked, hipStream_t st, long long* err_index);
-int codec_encode(int group, void* d_out, const void* d_in, size_t n, int compressed, hipStream_t st);
-// point_fft_g2.hip
-int point_fft_g2(void* d_points, uint32_t log_n, const Fr& omega, bool scale, const Fr& scale_canon, hipStream_t st, bool trusted_subgroup);
 int segsum_g1_device(const void* d_points, uint64_t nnz, const uint32_t* d_row_ptr, uint32_t n_rows, hipStream_t st, void* d_out);
 int segsum_g2_device(const void* d_points, uint64_t nnz, const uint32_t* d_row_ptr, uint32_t n_rows, hipStream_t st, void* d_out);
 void msm_release_g1();
@@ -44,6 +38,13 @@ void msm_release_g2();
 void msm_geometry(uint64_t n, uint32_t wgroups, uint32_t* c, uint32_t* W);
 int msm_selftest_digits(uint64_t n, uint32_t wgroups, const uint32_t scalar[8], uint32_t w_start, uint32_t w_stop, int direct, int32_t* digits,
                         uint32_t* geom);
+// point_fft.hip
+int point_fft_g1(void* d_points, uint32_t log_n, const Fr& omega, bool scale, const Fr& scale_canon, hipStream_t st);
+// codec.hip
+int codec_decode(int group, void* d_out, const void* d_in, size_t n, int compressed, int checked, hipStream_t st, long long* err_index);
+int codec_encode(int group, void* d_out, const void* d_in, size_t n, int compressed, hipStream_t st);
+// point_fft_g2.hip
+int point_fft_g2(void* d_points, uint32_t log_n, const Fr& omega, bool scale, const Fr& scale_canon, hipStream_t st, bool trusted_subgroup);
 
 // scalar_mul.hip
 // out[i] = k[i or 0] * P[i or base_index[i] or 0], affine (batched_accumulator.rs:1130-1181, parameters.rs:423-470); see the definition for the modes

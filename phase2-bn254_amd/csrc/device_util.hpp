@@ -30,7 +30,7 @@
 
 namespace zk {
 
-// A multiexp whose exponents arrive in CHUNKS: the host-buffer entry point (api.hip: msm_host_entry) uploads them over PCIe while
+// A multiexp whose exponents arrive in CHUNKS: the host-buffer entry point (host_entry.hip: msm_host_entry) uploads them over PCIe while
 // the kernels of the earlier chunks run.  msm_device (msm_impl.hpp) evaluates chunk c = exponents [cuts[c], cuts[c+1]) when told
 // where they are, with ONE geometry and ONE bucket array for the whole call.
 struct MsmChunks {

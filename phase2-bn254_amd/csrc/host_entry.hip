@@ -29,52 +29,81 @@
 namespace zk {
 thread_local long long t_last_err_index = -1;
 
-// Source / QueryDensity contract (source.rs:36-118, multiexp.rs:92): returns the number of exponents
-// to process, the exponent index of the first UnexpectedEof (or -1) and, for a density map, the
-// per-word exclusive prefix popcounts.
+// Source / QueryDensity contract (source.rs:36-118, multiexp.rs:92): the number of exponents to process, the exponent index of the
+// first UnexpectedEof (or -1) and, for a density map, the per-word exclusive prefix popcounts (one entry past the last word: the total).
 struct DensityPlan {
   uint64_t n = 0;
   long long eof_index = -1;
+  const uint32_t* density = nullptr;  // the caller's map (nullptr: FullDensity)
   std::vector<uint32_t> prefix;
+  uint64_t live() const { return eof_index >= 0 ? (uint64_t)eof_index : n; }  // exponents before the first Eof
+  // word w of the map without the bits of exponents >= n (the last word of an n that is no multiple of 32)
+  uint32_t word(uint64_t w) const { return (w + 1) * 32 > n ? density[w] & ((1u << (n & 31)) - 1u) : density[w]; }
+  // bases consumed by exponents [0, i), i <= n (i itself under FullDensity)
+  uint64_t rank(uint64_t i) const {
+    if (density == nullptr) return i;
+    const uint64_t r = prefix[i >> 5];
+    return (i & 31) ? r + (uint32_t)__builtin_popcount(word(i >> 5) & ((1u << (i & 31)) - 1u)) : r;
+  }
+  // the exponent that owns the r-th selected base (r itself under FullDensity); n when fewer than r + 1 bases are selected
+  uint64_t select(uint64_t r) const {
+    if (density == nullptr) return r;
+    if (r >= prefix.back()) return n;
+    uint64_t w = 0;
+    while (w + 2 < prefix.size() && prefix[w + 1] <= r) ++w;
+    uint32_t v = word(w);
+    for (uint64_t k = r - prefix[w]; k && v; --k) v &= v - 1;  // drop the set bits below the (r - prefix[w])-th
+    return w * 32 + (v ? (uint32_t)__builtin_ctz(v) : 32);
+  }
 };
 
-int plan_density(size_t n_bases, size_t base_offset, size_t n_scalars, const uint32_t* density, size_t density_bits, DensityPlan* P) {
-  uint64_t n = n_scalars;
-  if (density != nullptr && density_bits < n) n = density_bits;  // zip() stops at the shorter (multiexp.rs:92)
-  P->n = n;
-  uint64_t avail = base_offset < n_bases ? n_bases - base_offset : 0;
+DensityPlan plan_density(size_t n_bases, size_t base_offset, size_t n_scalars, const uint32_t* density, size_t density_bits) {
+  DensityPlan P;
+  P.density = density;
+  P.n = n_scalars;
+  if (density != nullptr && density_bits < P.n) P.n = density_bits;  // zip() stops at the shorter (multiexp.rs:92)
+  const uint64_t avail = base_offset < n_bases ? n_bases - base_offset : 0;
   if (density == nullptr) {
-    if (n > avail) P->eof_index = (long long)avail;
-    return ZK_OK;
+    if (P.n > avail) P.eof_index = (long long)avail;
+    return P;
   }
-  uint64_t words = (n + 31) / 32;
-  P->prefix.resize(words ? words : 1);
+  const uint64_t words = (P.n + 31) / 32;
+  P.prefix.resize(words + 1);
   uint64_t used = 0;
   for (uint64_t w = 0; w < words; ++w) {
-    P->prefix[w] = (uint32_t)used;
-    uint32_t v = density[w];
-    if (w == words - 1 && (n & 31)) v &= (1u << (n & 31)) - 1u;
-    uint32_t pc = (uint32_t)__builtin_popcount(v);
-    if (P->eof_index < 0 && used + pc > avail) {
-      // the (avail - used + 1)-th set bit of this word is the first exponent without a base
-      uint64_t need = avail - used;
-      for (uint32_t b = 0; b < 32; ++b)
-        if ((v >> b) & 1) {
-          if (need == 0) { P->eof_index = (long long)(w * 32 + b); break; }
-          --need;
-        }
-    }
-    used += pc;
+    P.prefix[w] = (uint32_t)used;
+    used += (uint32_t)__builtin_popcount(P.word(w));
   }
-  return ZK_OK;
+  P.prefix[words] = (uint32_t)used;
+  if (used > avail) P.eof_index = (long long)P.select(avail);  // the (avail + 1)-th selected exponent is the first without a base
+  return P;
 }
 
-// device copies of density maps (words + prefix popcounts): grow-only buffers, leased per call
-struct DensityPool {
-  struct Buf {
+// a grow-only device allocation.  reserve() regrows by free + malloc: the owner knows that nothing queued still uses the old one
+struct DevBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  int reserve(size_t want) {
+    if (bytes >= want) return ZK_OK;
+    if (p) ZK_HIP(hipFree(p));
+    p = nullptr;
+    bytes = 0;
+    ZK_HIP(hipMalloc(&p, want));
+    bytes = want;
+    return ZK_OK;
+  }
+  void release() {  // (on the current device)
+    (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+};
+
+// the device buffers of the host-buffer entry points (a call's uploads and results; msm_dev_entry's copy of a density map): grow-only
+// buffers, leased per call -- hipMalloc / hipFree per call would synchronise the whole device and with it every other thread's multiexp
+struct DeviceBufPool {
+  struct Buf : DevBuf {
     int dev = -1;
-    void* p = nullptr;
-    size_t bytes = 0;
     bool busy = false;
   };
   static std::mutex& mu() { static std::mutex m; return m; }
@@ -99,21 +128,16 @@ struct DensityPool {
         }
         b->busy = true;
       }
-      if (b->bytes < bytes) {
-        if (b->p) ZK_HIP(hipFree(b->p));  // idle: its last user's stream was synchronised before the release
-        b->p = nullptr;
-        b->bytes = 0;
-        ZK_HIP(hipMalloc(&b->p, bytes));
-        b->bytes = bytes;
-      }
-      return ZK_OK;
+      return b->reserve(bytes);  // (idle: its last user's stream was synchronised before the release)
     }
-    ~Lease() {
+    void release() {
       if (b == nullptr) return;
       (void)hipStreamSynchronize(st);  // (idle already after a completed call: the result came back over this stream)
       std::lock_guard<std::mutex> lk(mu());
       b->busy = false;
+      b = nullptr;
     }
+    ~Lease() { release(); }
   };
 };
 
@@ -127,23 +151,21 @@ int msm_dev_entry(const void* d_bases, size_t n_bases, size_t base_offset, const
   if (!out_xyz || (n_scalars && !d_scalars && !chunks) || (n_bases && !d_bases)) return ZK_ERR_BAD_ARGS;
   if (n_bases >= (1ull << 31) || n_scalars >= (1ull << 31)) return ZK_ERR_BAD_ARGS;
   hipStream_t st = (hipStream_t)stream;
-  DensityPlan P;
-  int rc = plan_density(n_bases, base_offset, n_scalars, density, density_bits, &P);
-  if (rc) return rc;
-  uint64_t n = P.eof_index >= 0 ? (uint64_t)P.eof_index : P.n;  // exponents before the first Eof
+  const DensityPlan P = plan_density(n_bases, base_offset, n_scalars, density, density_bits);
+  const uint64_t n = P.live();
+  int rc = ZK_OK;
   uint32_t* d_density = nullptr;
   uint32_t* d_prefix = nullptr;
-  DensityPool::Lease density_lease;
+  DeviceBufPool::Lease density_lease;
   if (density != nullptr && n > 0) {
-    // leased from a small pool for the duration of the call: hipMalloc / hipFree per call would synchronise the whole device and
-    // with it every other thread's multiexp, and a buffer per host thread would outlive short-lived caller threads
+    // the device copy of the map (words + prefix popcounts), leased on the caller's stream for the duration of the call (a buffer per
+    // host thread would outlive short-lived caller threads)
     int dev = 0;
     ZK_HIP(hipGetDevice(&dev));
     size_t words = (n + 31) / 32;
     rc = density_lease.acquire(dev, words * 8, st);
     if (rc) return rc;
-    DensityPool::Buf& buf = *density_lease.b;
-    d_density = (uint32_t*)buf.p;
+    d_density = (uint32_t*)density_lease.b->p;
     d_prefix = d_density + words;
     ZK_HIP(hipMemcpyAsync(d_density, density, words * 4, hipMemcpyHostToDevice, st));
     ZK_HIP(hipMemcpyAsync(d_prefix, P.prefix.data(), words * 4, hipMemcpyHostToDevice, st));
@@ -160,20 +182,7 @@ int msm_dev_entry(const void* d_bases, size_t n_bases, size_t base_offset, const
   if (rc == ZK_ERR_UNEXPECTED_IDENTITY) {
     // the kernels report the lowest BASE index that was the identity under a non-zero exponent; the exponent that owns it
     // is the (index - base_offset)-th selected one (source.rs:101-118): itself under FullDensity
-    long long rank = err_index - (long long)base_offset;
-    if (density != nullptr) {
-      size_t w = 0;
-      const size_t words = (n + 31) / 32;
-      while (w + 1 < words && (long long)P.prefix[w + 1] <= rank) ++w;
-      uint32_t word = density[w];
-      if ((w + 1) * 32 > n) word &= (n & 31) ? ((1u << (n & 31)) - 1u) : 0xffffffffu;
-      long long need = rank - (long long)P.prefix[w];
-      uint32_t b = 0;
-      for (; b < 32; ++b)
-        if ((word >> b) & 1u) { if (need == 0) break; --need; }
-      rank = (long long)(w * 32 + b);
-    }
-    t_last_err_index = rank;
+    t_last_err_index = (long long)P.select((uint64_t)(err_index - (long long)base_offset));
     return rc;
   }
   if (rc == ZK_ERR_BAD_ARGS) t_last_err_index = err_index;  // a non-canonical exponent (>= 2^254): its index
@@ -347,40 +356,35 @@ void bases_drop(const std::shared_ptr<BasesEntry>& e) {  // a failed upload
   e->d = e->table = nullptr;
   e->table_bytes = 0;
 }
+struct FillGuard {  // whatever happens, the entry a call fills is either ready or gone when the call returns
+  std::shared_ptr<BasesEntry> e;
+  bool fill, ok = false;
+  ~FillGuard() {
+    if (!fill) return;
+    e->ready = ok;
+    e->fill_mu.unlock();
+    if (!ok) bases_drop(e);
+  }
+};
 
 // two staging buffers for scalar chunks, a bases buffer for uncached calls, the two streams.  Leased from a pool for the duration
 // of a call (callers come and go -- the prover queues its multiexps from short-lived threads -- and their buffers must not pile up)
 struct HostStage {
   int dev = -1;
   bool busy = false;
-  void* sc[2] = {nullptr, nullptr};
-  size_t sc_bytes = 0;
-  void* bases = nullptr;
-  size_t bases_bytes = 0;
-  void* raw = nullptr;      // strided records: one bounded piece of the caller's raw records on its way to records_pack
-  size_t raw_bytes = 0;
+  DevBuf sc[2];   // the scalar chunks' staging buffers
+  DevBuf bases;
+  DevBuf raw;     // strided records: one bounded piece of the caller's raw records on its way to records_pack
   hipStream_t copy = nullptr, compute = nullptr;
 };
 std::mutex g_stage_mu;
 std::vector<HostStage*> g_stages;  // the pool: as many stages as there have been concurrent host-buffer calls
-struct StageLease {
-  HostStage* s = nullptr;
-  ~StageLease() {
-    if (s == nullptr) return;
-    // every exit of msm_host_entry has joined its copy thread; the compute stream is idle after the last chunk's result came back,
-    // except on an error path
-    (void)hipStreamSynchronize(s->compute);
-    (void)hipStreamSynchronize(s->copy);
-    std::lock_guard<std::mutex> lk(g_stage_mu);
-    s->busy = false;
-  }
-};
-HostStage* host_stage(int dev, StageLease* lease) {
+HostStage* host_stage(int dev) {  // an idle stage of the device, marked busy (nullptr: no streams to be had)
   HostStage* mine = nullptr;
   {
     std::lock_guard<std::mutex> lk(g_stage_mu);
     for (HostStage* s : g_stages)  // the idle stage of this device with the largest staging buffers
-      if (!s->busy && s->dev == dev && (mine == nullptr || s->sc_bytes > mine->sc_bytes)) mine = s;
+      if (!s->busy && s->dev == dev && (mine == nullptr || s->sc[0].bytes + s->sc[1].bytes > mine->sc[0].bytes + mine->sc[1].bytes)) mine = s;
     if (mine) mine->busy = true;
   }
   if (mine == nullptr) {
@@ -395,18 +399,34 @@ HostStage* host_stage(int dev, StageLease* lease) {
     std::lock_guard<std::mutex> lk(g_stage_mu);
     g_stages.push_back(mine);
   }
-  lease->s = mine;
   return mine;
 }
-int stage_reserve(void** p, size_t* have, size_t want) {
-  if (*have >= want) return ZK_OK;
-  if (*p) ZK_HIP(hipFree(*p));
-  *p = nullptr;
-  *have = 0;
-  ZK_HIP(hipMalloc(p, want));
-  *have = want;
-  return ZK_OK;
-}
+// What a host-buffer call holds while it runs: a stage (its two streams) and, with bytes > 0, one buffer of the pool.  On every exit
+// both streams are idle before the buffer and then the stage go back: every exit of msm_host_run has joined its copy thread and the
+// compute stream is idle after the last result came back, but an error path may leave work queued, copies into the buffer included.
+struct CallLease {
+  HostStage* S = nullptr;
+  void* buf = nullptr;
+  int open(int dev, size_t bytes = 0) {
+    S = host_stage(dev);
+    if (S == nullptr) return ZK_ERR_DEVICE;
+    if (bytes == 0) return ZK_OK;
+    const int rc = pooled_.acquire(dev, bytes, S->compute);
+    if (rc == ZK_OK) buf = pooled_.b->p;
+    return rc;
+  }
+  ~CallLease() {
+    if (S == nullptr) return;
+    (void)hipStreamSynchronize(S->compute);
+    (void)hipStreamSynchronize(S->copy);
+    pooled_.release();
+    std::lock_guard<std::mutex> lk(g_stage_mu);
+    S->busy = false;
+  }
+
+ private:
+  DeviceBufPool::Lease pooled_;
+};
 
 // forget the device copies of the base vector at `host` (nullptr: of every vector); entries in use stay until their call ends
 void bases_cache_invalidate(const void* host) {
@@ -440,16 +460,12 @@ void host_entry_release_all() {
   std::lock_guard<std::mutex> lk(g_stage_mu);
   for (HostStage* s : g_stages) {
     (void)hipSetDevice(s->dev);
-    (void)hipFree(s->sc[0]); (void)hipFree(s->sc[1]); (void)hipFree(s->bases); (void)hipFree(s->raw);
-    s->sc[0] = s->sc[1] = s->bases = s->raw = nullptr;
-    s->sc_bytes = s->bases_bytes = s->raw_bytes = 0;
+    for (DevBuf* b : {&s->sc[0], &s->sc[1], &s->bases, &s->raw}) b->release();
   }
-  std::lock_guard<std::mutex> dl(DensityPool::mu());
-  for (DensityPool::Buf* b : DensityPool::all()) {
+  std::lock_guard<std::mutex> dl(DeviceBufPool::mu());
+  for (DeviceBufPool::Buf* b : DeviceBufPool::all()) {
     (void)hipSetDevice(b->dev);
-    (void)hipFree(b->p);
-    b->p = nullptr;
-    b->bytes = 0;
+    b->release();
   }
 }
 
@@ -487,93 +503,41 @@ const void* bases_table(const std::shared_ptr<BasesEntry>& e, hipStream_t st) {
   return t;
 }
 
+// a call's events (no timing), destroyed with it
+struct Events {
+  std::vector<hipEvent_t> e;
+  explicit Events(size_t count) : e(count, nullptr) {}
+  hipError_t create() {
+    hipError_t rc = hipSuccess;
+    for (size_t i = 0; i < e.size() && rc == hipSuccess; ++i) rc = hipEventCreateWithFlags(&e[i], hipEventDisableTiming);
+    return rc;
+  }
+  ~Events() {
+    for (hipEvent_t x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+  hipEvent_t operator[](size_t i) const { return e[i]; }
+};
+
+bool trace_host() {  // MI355ZK_TRACE_HOST: timeline of the streamed / multi-device call on stderr
+  static const bool on = std::getenv("MI355ZK_TRACE_HOST") != nullptr;
+  return on;
+}
+double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+
+// the argument rules of the host-buffer multiexp (include/mi355zk.h: rc 3)
+bool msm_host_args_ok(const void* bases, size_t n_bases, const void* scalars, size_t n_scalars, const void* out_xyz) {
+  return out_xyz && (!n_scalars || scalars) && (!n_bases || bases) && n_bases < (1ull << 31) && n_scalars < (1ull << 31);
+}
+
 constexpr uint64_t HOST_CHUNK_UPLOAD = 1ull << 23;  // exponents per chunk of a streamed call whose bases travel too (link-bound)
 constexpr uint64_t HOST_CHUNK_MIN = 1ull << 21;     // smallest first chunk of a call whose bases are on the device; below 4 of these the call is not cut
 
-// One host-buffer multiexp on the calling thread's CURRENT device.  (wgroups, wgroup): only that group of scalar windows (a cell of
-// the single-process multi-GPU mode below; (1, 0) is the whole multiexp).
-// L: the layout of the host records (packed by default; strided records are repacked on the device as they arrive).
-template <int GROUP>
-int msm_host_run(const uint8_t* bases, size_t n_bases, size_t base_offset, const uint64_t* scalars, size_t n_scalars,
-                 const uint32_t* density, size_t density_bits, uint64_t* out_xyz, const RecordLayout& L = RecordLayout(),
-                 uint32_t wgroups = 1, uint32_t wgroup = 0) {
-  t_last_err_index = -1;
-  if (!out_xyz || (n_scalars && !scalars) || (n_bases && !bases)) return ZK_ERR_BAD_ARGS;
-  if (n_bases >= (1ull << 31) || n_scalars >= (1ull << 31)) return ZK_ERR_BAD_ARGS;
-  constexpr size_t bsz = GROUP == 1 ? 64 : 128;
-  constexpr size_t jac_words = GROUP == 1 ? 12 : 24;
-  const size_t hs = L.host_stride(GROUP);  // bytes per HOST record
-  int dev = 0;
-  ZK_HIP(hipGetDevice(&dev));
-  StageLease stage_lease;
-  HostStage* S = host_stage(dev, &stage_lease);
-  if (S == nullptr) return ZK_ERR_DEVICE;
-
-  // the exponents this call evaluates and the bases they consume (source.rs:36-118)
-  DensityPlan P;
-  int rc = plan_density(n_bases, base_offset, n_scalars, density, density_bits, &P);
-  if (rc) return rc;
-  const uint64_t n = P.eof_index >= 0 ? (uint64_t)P.eof_index : P.n;   // exponents before the first Eof
-  auto rank_of = [&](uint64_t i) -> uint64_t {                          // bases consumed by exponents [0, i)
-    if (density == nullptr) return i;
-    if (i == 0) return 0;
-    const uint64_t w = i >> 5;
-    uint64_t r = w < P.prefix.size() ? P.prefix[w] : 0;
-    if (w >= P.prefix.size()) {  // i == n on a word boundary past the last planned word
-      const uint64_t lw = P.prefix.size() - 1;
-      uint32_t v = density[lw];
-      if ((lw + 1) * 32 > P.n) v &= (P.n & 31) ? ((1u << (P.n & 31)) - 1u) : 0xffffffffu;
-      return P.prefix[lw] + (uint32_t)__builtin_popcount(v);
-    }
-    if (i & 31) r += (uint32_t)__builtin_popcount(density[w] & ((1u << (i & 31)) - 1u));
-    return r;
-  };
-
-  // ---- bases: cached, being cached by this call, or (not pinned / cache off / full) the leased stage's buffer
-  bool fill = false;
-  std::shared_ptr<BasesEntry> entry = n_bases ? bases_lookup(bases, n_bases, GROUP, n_bases * bsz, dev, &fill, L) : nullptr;
-  void* d_bases = entry ? entry->d : nullptr;
-  bool upload_bases = fill;
-  if (!entry && n_bases) {
-    rc = stage_reserve(&S->bases, &S->bases_bytes, n_bases * bsz);
-    if (rc) return rc;
-    d_bases = S->bases;
-    upload_bases = true;
-  }
-  struct FillGuard {  // whatever happens, the entry is either ready or gone when this call returns
-    std::shared_ptr<BasesEntry> e;
-    bool fill, ok = false;
-    ~FillGuard() {
-      if (!fill) return;
-      e->ready = ok;
-      e->fill_mu.unlock();
-      if (!ok) bases_drop(e);
-    }
-  } guard{entry, fill};
-  // bases [lo, hi) -> d_bases, enqueued on the copy stream.  Packed records go straight over the link.  Strided records go raw, in pieces of
-  // at most RAW_PIECE records, into the stage's raw buffer, and records_pack repacks each piece into d_bases behind its copy; the copy
-  // stream's order keeps a piece from overwriting the raw buffer before the previous piece's repack has read it.  The device memory on
-  // top of the packed copy is one piece, not the vector.
-  constexpr uint64_t RAW_PIECE = 1ull << 19;
-  if (!L.packed() && n_bases && upload_bases) {
-    rc = stage_reserve(&S->raw, &S->raw_bytes, (size_t)std::min<uint64_t>(n_bases, RAW_PIECE) * hs);
-    if (rc) return rc;
-  }
-  auto put_bases = [&](uint64_t lo, uint64_t hi) -> hipError_t {
-    if (hi <= lo) return hipSuccess;
-    if (L.packed()) return hipMemcpyAsync((char*)d_bases + lo * bsz, bases + lo * bsz, (hi - lo) * bsz, hipMemcpyHostToDevice, S->copy);
-    for (uint64_t p = lo; p < hi; p += RAW_PIECE) {
-      const uint64_t m = std::min<uint64_t>(RAW_PIECE, hi - p);
-      hipError_t e = hipMemcpyAsync(S->raw, bases + p * hs, m * hs, hipMemcpyHostToDevice, S->copy);
-      if (e != hipSuccess) return e;
-      if (records_pack_run(GROUP, S->raw, m, L, (char*)d_bases + p * bsz, S->copy) != ZK_OK) return hipErrorLaunchFailure;
-    }
-    return hipSuccess;
-  };
-
-  // ---- chunks (cut at multiples of 32 exponents, so that density words are not shared between chunks).  Every chunk runs digits ->
-  // partition -> accumulate into the ONE bucket array of the call (msm_device, MsmChunks); what a chunk costs on top of its share
-  // of the work is the re-partition of the bucket bounds and one read + write of every bucket record it touches (~1.3 ms at 2^26).
+// The chunk schedule of a streamed call of n exponents: cuts[c] .. cuts[c + 1] is chunk c (cut at multiples of 32 exponents, so that density
+// words are not shared between chunks; n == 0: no chunk).  Every chunk runs digits -> partition -> accumulate into the ONE bucket array of
+// the call (msm_device, MsmChunks); what a chunk costs on top of its share of the work is the re-partition of the bucket bounds and one
+// read + write of every bucket record it touches (~1.3 ms at 2^26).
+std::vector<uint64_t> host_chunk_cuts(uint64_t n, bool upload_bases) {
   std::vector<uint64_t> cuts{0};
   const char* env_grow = std::getenv("MI355ZK_HOST_CHUNK_GROWTH");  // percent (read per call: tools/exp_host_chunks.py sweeps it in one process)
   const char* env_first = std::getenv("MI355ZK_HOST_CHUNK_FIRST");  // log2 of the first chunk (bases on the device)
@@ -608,103 +572,174 @@ int msm_host_run(const uint8_t* bases, size_t n_bases, size_t base_offset, const
     }
   }
   if (n) cuts.push_back(n);
+  return cuts;
+}
+
+// Host records [lo, hi) of a base vector -> the packed device copy, enqueued on the stage's copy stream.  Packed records go straight over the
+// link.  Strided records go raw, in pieces of at most RAW_PIECE records, into the stage's raw buffer, and records_pack repacks each piece into
+// the copy behind its upload; the copy stream's order keeps a piece from overwriting the raw buffer before the previous piece's repack has
+// read it.  The device memory on top of the packed copy is one piece, not the vector.
+constexpr uint64_t RAW_PIECE = 1ull << 19;
+struct BaseUpload {
+  const uint8_t* host;
+  void* dev;
+  int group;
+  const RecordLayout& L;
+  HostStage* S;
+  hipError_t put(uint64_t lo, uint64_t hi) const {
+    if (hi <= lo) return hipSuccess;
+    const size_t bsz = group == 1 ? 64 : 128, hs = L.host_stride(group);
+    if (L.packed()) return hipMemcpyAsync((char*)dev + lo * bsz, host + lo * bsz, (hi - lo) * bsz, hipMemcpyHostToDevice, S->copy);
+    for (uint64_t p = lo; p < hi; p += RAW_PIECE) {
+      const uint64_t m = std::min<uint64_t>(RAW_PIECE, hi - p);
+      hipError_t e = hipMemcpyAsync(S->raw.p, host + p * hs, m * hs, hipMemcpyHostToDevice, S->copy);
+      if (e != hipSuccess) return e;
+      if (records_pack_run(group, S->raw.p, m, L, (char*)dev + p * bsz, S->copy) != ZK_OK) return hipErrorLaunchFailure;
+    }
+    return hipSuccess;
+  }
+};
+
+// What the compute side (msm_device through MsmChunks) and the copy thread of a streamed call share.  staging[c & 1] is free again once the
+// DIGIT kernel of chunk c - 2 -- the only reader of a chunk's exponents -- has run: the compute side records an event behind it.
+struct Feed : MsmChunks {
+  std::mutex mu;
+  std::condition_variable cv;
+  uint64_t copied = 0, digits = 0;          // chunks uploaded / chunks whose digit kernel has been enqueued
+  bool copy_failed = false, abort_copy = false;
+  void* sc[2];
+  Events ev;                                // ev[c]: recorded behind chunk c's digit kernel
+  Feed(const std::vector<uint64_t>& chunk_cuts, const HostStage* S) : sc{S->sc[0].p, S->sc[1].p}, ev(chunk_cuts.size() - 1) {
+    n_chunks = (uint32_t)(chunk_cuts.size() - 1);
+    cuts = chunk_cuts.data();
+  }
+  int acquire(uint32_t c, hipStream_t, const void** d) override {
+    std::unique_lock<std::mutex> lk(mu);
+    cv.wait(lk, [&] { return copy_failed || copied > c; });  // (a host-side wait: the earlier chunks' kernels are already queued)
+    if (copy_failed) return ZK_ERR_DEVICE;
+    *d = sc[c & 1];
+    return ZK_OK;
+  }
+  int digits_enqueued(uint32_t c, hipStream_t st) override {
+    ZK_HIP(hipEventRecord(ev[c], st));
+    std::lock_guard<std::mutex> lk(mu);
+    digits = c + 1;
+    cv.notify_all();
+    return ZK_OK;
+  }
+};
+
+// The copy thread: for chunk c, scalars -> staging[c & 1] and (when uploading) the bases the chunk consumes; afterwards (complete_entry) the
+// bases outside the consumed range, so that a cache entry is complete.
+struct CopyJob {
+  int dev;
+  const uint64_t* scalars;
+  const DensityPlan& P;
+  uint64_t n_bases, base_offset;
+  bool upload_bases, complete_entry;
+  const BaseUpload& up;
+  std::chrono::steady_clock::time_point t0;
+};
+void copy_chunks(Feed& feed, const CopyJob& J) {
+  auto fail = [&] { std::lock_guard<std::mutex> lk(feed.mu); feed.copy_failed = true; feed.cv.notify_all(); };
+  if (hipSetDevice(J.dev) != hipSuccess) { fail(); return; }
+  hipStream_t copy = J.up.S->copy;
+  const uint64_t b_lo = J.base_offset < J.n_bases ? J.base_offset : J.n_bases;
+  uint64_t b_done = b_lo;  // bases [b_lo, b_done) are on the device
+  for (uint64_t c = 0; c < feed.n_chunks; ++c) {
+    if (c >= 2) {
+      {
+        std::unique_lock<std::mutex> lk(feed.mu);
+        feed.cv.wait(lk, [&] { return feed.abort_copy || feed.digits >= c - 1; });
+        if (feed.abort_copy) return;
+      }
+      if (hipEventSynchronize(feed.ev[c - 2]) != hipSuccess) { fail(); return; }
+    } else {
+      std::lock_guard<std::mutex> lk(feed.mu);
+      if (feed.abort_copy) return;
+    }
+    const uint64_t lo = feed.cuts[c], hi = feed.cuts[c + 1];
+    hipError_t e = hipMemcpyAsync(feed.sc[c & 1], J.scalars + lo * 4, (hi - lo) * 32, hipMemcpyHostToDevice, copy);
+    if (e == hipSuccess && J.upload_bases) {
+      uint64_t b_hi = J.base_offset + J.P.rank(hi);
+      if (b_hi > J.n_bases) b_hi = J.n_bases;
+      if (b_hi > b_done) {
+        e = J.up.put(b_done, b_hi);
+        b_done = b_hi;
+      }
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(copy);
+    if (e != hipSuccess) { fail(); return; }
+    if (trace_host()) std::fprintf(stderr, "[mi355zk] host entry: chunk %llu (%llu exponents) uploaded at %.2f ms\n", (unsigned long long)c, (unsigned long long)(hi - lo), ms_since(J.t0));
+    std::lock_guard<std::mutex> lk(feed.mu);
+    feed.copied = c + 1;
+    feed.cv.notify_all();
+  }
+  if (J.complete_entry) {  // the rest of the vector (not needed by this call) completes the cache entry
+    hipError_t e = hipSuccess;
+    if (b_lo > 0) e = J.up.put(0, b_lo);
+    if (e == hipSuccess && b_done < J.n_bases) e = J.up.put(b_done, J.n_bases);
+    if (e == hipSuccess) e = hipStreamSynchronize(copy);
+    if (e != hipSuccess) fail();
+  }
+}
+
+// One host-buffer multiexp on the calling thread's CURRENT device.  (wgroups, wgroup): only that group of scalar windows (a cell of
+// the single-process multi-GPU mode below; (1, 0) is the whole multiexp).
+// L: the layout of the host records (packed by default; strided records are repacked on the device as they arrive).
+template <int GROUP>
+int msm_host_run(const uint8_t* bases, size_t n_bases, size_t base_offset, const uint64_t* scalars, size_t n_scalars,
+                 const uint32_t* density, size_t density_bits, uint64_t* out_xyz, const RecordLayout& L = RecordLayout(),
+                 uint32_t wgroups = 1, uint32_t wgroup = 0) {
+  t_last_err_index = -1;
+  if (!msm_host_args_ok(bases, n_bases, scalars, n_scalars, out_xyz)) return ZK_ERR_BAD_ARGS;
+  constexpr size_t bsz = GROUP == 1 ? 64 : 128;
+  constexpr size_t jac_words = GROUP == 1 ? 12 : 24;
+  int dev = 0;
+  ZK_HIP(hipGetDevice(&dev));
+  CallLease lease;
+  int rc = lease.open(dev);
+  if (rc) return rc;
+  HostStage* S = lease.S;
+
+  // ---- plan: the exponents this call evaluates and the bases they consume (source.rs:36-118)
+  const DensityPlan P = plan_density(n_bases, base_offset, n_scalars, density, density_bits);
+  const uint64_t n = P.live();
+
+  // ---- bases: cached, being cached by this call, or (not pinned / cache off / full) the leased stage's buffer
+  bool fill = false;
+  std::shared_ptr<BasesEntry> entry = n_bases ? bases_lookup(bases, n_bases, GROUP, n_bases * bsz, dev, &fill, L) : nullptr;
+  void* d_bases = entry ? entry->d : nullptr;
+  bool upload_bases = fill;
+  if (!entry && n_bases) {
+    rc = S->bases.reserve(n_bases * bsz);
+    if (rc) return rc;
+    d_bases = S->bases.p;
+    upload_bases = true;
+  }
+  FillGuard guard{entry, fill};
+  if (!L.packed() && n_bases && upload_bases) {
+    rc = S->raw.reserve((size_t)std::min<uint64_t>(n_bases, RAW_PIECE) * L.host_stride(GROUP));
+    if (rc) return rc;
+  }
+  const BaseUpload up{bases, d_bases, GROUP, L, S};
+
+  // ---- cuts, and the two staging buffers of the largest chunk
+  const std::vector<uint64_t> cuts = host_chunk_cuts(n, upload_bases);
   const uint64_t n_chunks = cuts.size() - 1;
   uint64_t max_chunk = 0;
   for (uint64_t c = 0; c < n_chunks; ++c) max_chunk = std::max(max_chunk, cuts[c + 1] - cuts[c]);
-  const size_t sc_bytes = (size_t)max_chunk * 32;
-  if (n) {
-    for (int k = 0; k < 2; ++k) {
-      size_t have = S->sc_bytes;
-      rc = stage_reserve(&S->sc[k], &have, sc_bytes);
-      if (rc) { S->sc_bytes = 0; return rc; }
-    }
-    if (S->sc_bytes < sc_bytes) S->sc_bytes = sc_bytes;
+  for (int k = 0; k < 2 && n; ++k) {
+    rc = S->sc[k].reserve((size_t)max_chunk * 32);
+    if (rc) return rc;
   }
 
-  // The copy thread: for chunk c, scalars -> staging[c & 1] and (when uploading) the bases the chunk consumes; afterwards the
-  // bases outside the consumed range, so that a cache entry is complete.  staging[c & 1] is free again once the DIGIT kernel of
-  // chunk c - 2 -- the only reader of a chunk's exponents -- has run: the compute side records an event behind it.
-  struct Feed : MsmChunks {
-    std::mutex mu;
-    std::condition_variable cv;
-    uint64_t copied = 0, digits = 0;          // chunks uploaded / chunks whose digit kernel has been enqueued
-    bool copy_failed = false, abort_copy = false;
-    void* sc[2] = {nullptr, nullptr};
-    std::vector<hipEvent_t> ev;               // ev[c]: recorded behind chunk c's digit kernel
-    int acquire(uint32_t c, hipStream_t, const void** d) override {
-      std::unique_lock<std::mutex> lk(mu);
-      cv.wait(lk, [&] { return copy_failed || copied > c; });  // (a host-side wait: the earlier chunks' kernels are already queued)
-      if (copy_failed) return ZK_ERR_DEVICE;
-      *d = sc[c & 1];
-      return ZK_OK;
-    }
-    int digits_enqueued(uint32_t c, hipStream_t st) override {
-      ZK_HIP(hipEventRecord(ev[c], st));
-      std::lock_guard<std::mutex> lk(mu);
-      digits = c + 1;
-      cv.notify_all();
-      return ZK_OK;
-    }
-    ~Feed() override {
-      for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
-  } feed;
-  feed.n_chunks = (uint32_t)n_chunks;
-  feed.cuts = cuts.data();
-  feed.sc[0] = S->sc[0];
-  feed.sc[1] = S->sc[1];
-  feed.ev.reserve(n_chunks);
-  for (uint64_t c = 0; c < n_chunks; ++c) {
-    hipEvent_t e;
-    ZK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    feed.ev.push_back(e);
-  }
-  const uint64_t b_lo = base_offset < n_bases ? base_offset : n_bases;
-  static const bool trace = std::getenv("MI355ZK_TRACE_HOST") != nullptr;  // timeline of the streamed call on stderr
-  const auto t0 = std::chrono::steady_clock::now();
-  auto ms_now = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-  auto copy_fn = [&]() {
-    auto fail = [&] { std::lock_guard<std::mutex> lk(feed.mu); feed.copy_failed = true; feed.cv.notify_all(); };
-    if (hipSetDevice(dev) != hipSuccess) { fail(); return; }
-    uint64_t b_done = b_lo;  // bases [b_lo, b_done) are on the device
-    for (uint64_t c = 0; c < n_chunks; ++c) {
-      if (c >= 2) {
-        {
-          std::unique_lock<std::mutex> lk(feed.mu);
-          feed.cv.wait(lk, [&] { return feed.abort_copy || feed.digits >= c - 1; });
-          if (feed.abort_copy) return;
-        }
-        if (hipEventSynchronize(feed.ev[c - 2]) != hipSuccess) { fail(); return; }
-      } else {
-        std::lock_guard<std::mutex> lk(feed.mu);
-        if (feed.abort_copy) return;
-      }
-      const uint64_t lo = cuts[c], hi = cuts[c + 1];
-      hipError_t e = hipMemcpyAsync(S->sc[c & 1], scalars + lo * 4, (hi - lo) * 32, hipMemcpyHostToDevice, S->copy);
-      if (e == hipSuccess && upload_bases) {
-        uint64_t b_hi = base_offset + rank_of(hi);
-        if (b_hi > n_bases) b_hi = n_bases;
-        if (b_hi > b_done) {
-          e = put_bases(b_done, b_hi);
-          b_done = b_hi;
-        }
-      }
-      if (e == hipSuccess) e = hipStreamSynchronize(S->copy);
-      if (e != hipSuccess) { fail(); return; }
-      if (trace) std::fprintf(stderr, "[mi355zk] host entry: chunk %llu (%llu exponents) uploaded at %.2f ms\n", (unsigned long long)c, (unsigned long long)(hi - lo), ms_now());
-      std::lock_guard<std::mutex> lk(feed.mu);
-      feed.copied = c + 1;
-      feed.cv.notify_all();
-    }
-    if (upload_bases && entry) {  // the rest of the vector (not needed by this call) completes the cache entry
-      hipError_t e = hipSuccess;
-      if (b_lo > 0) e = put_bases(0, b_lo);
-      if (e == hipSuccess && b_done < n_bases) e = put_bases(b_done, n_bases);
-      if (e == hipSuccess) e = hipStreamSynchronize(S->copy);
-      if (e != hipSuccess) fail();
-    }
-  };
+  // ---- feed
+  Feed feed(cuts, S);
+  ZK_HIP(feed.ev.create());
+  const CopyJob job{dev, scalars, P, n_bases, base_offset, upload_bases, upload_bases && entry, up, std::chrono::steady_clock::now()};
 
+  // ---- run
   uint64_t result_xyz[jac_words];
   {
     // a call that evaluates no exponent returns the reference's Projective::zero() = (0, 1, 0) (ec.rs:229-235), as msm_device does
@@ -717,7 +752,7 @@ int msm_host_run(const uint8_t* bases, size_t n_bases, size_t base_offset, const
   long long err_idx = -1;
   bool aborted = false;
   if (n_chunks > 0) {
-    std::thread copier(copy_fn);
+    std::thread copier([&] { copy_chunks(feed, job); });
     // a vector pinned WITH TABLES, already on the device, in a call that is not cut: table mode
     // (not for a handful of exponents over a long vector -- the prover's input multiexps over its 2^20-point a / b queries: the
     // table's window width comes from the VECTOR's length, and zeroing + reducing 2^19 buckets for a few points costs more than the
@@ -727,7 +762,7 @@ int msm_host_run(const uint8_t* bases, size_t n_bases, size_t base_offset, const
     result = msm_dev_entry<GROUP>(d_table ? d_table : d_bases, n_bases, base_offset, nullptr, n_scalars, density, density_bits, (void*)S->compute, result_xyz,
                                   wgroups, wgroup, 0, &feed, d_table != nullptr);
     err_idx = t_last_err_index;
-    if (trace) std::fprintf(stderr, "[mi355zk] host entry: result at %.2f ms (%llu chunks)\n", ms_now(), (unsigned long long)n_chunks);
+    if (trace_host()) std::fprintf(stderr, "[mi355zk] host entry: result at %.2f ms (%llu chunks)\n", ms_since(job.t0), (unsigned long long)n_chunks);
     {
       std::lock_guard<std::mutex> lk(feed.mu);
       // a call that failed before it had taken every chunk leaves the copy thread waiting: release it
@@ -737,9 +772,9 @@ int msm_host_run(const uint8_t* bases, size_t n_bases, size_t base_offset, const
     }
     copier.join();
     if (feed.copy_failed) result = ZK_ERR_DEVICE;
-  } else if (upload_bases && entry && n_bases) {
+  } else if (job.complete_entry && n_bases) {
     // nothing to evaluate, but the entry was created: fill it
-    hipError_t e = put_bases(0, n_bases);
+    hipError_t e = up.put(0, n_bases);
     if (e == hipSuccess) e = hipStreamSynchronize(S->copy);
     if (e != hipSuccess) result = ZK_ERR_DEVICE;
     if (result == ZK_OK && P.eof_index >= 0) { result = ZK_ERR_UNEXPECTED_EOF; err_idx = P.eof_index; }
@@ -747,6 +782,8 @@ int msm_host_run(const uint8_t* bases, size_t n_bases, size_t base_offset, const
     result = ZK_ERR_UNEXPECTED_EOF;
     err_idx = P.eof_index;
   }
+
+  // ---- join
   guard.ok = result != ZK_ERR_DEVICE && !feed.copy_failed && !(fill && aborted);  // an aborted streamed upload is incomplete
   t_last_err_index = err_idx;
   if (result != ZK_OK && result != ZK_ERR_UNEXPECTED_EOF) return result;
@@ -778,31 +815,48 @@ std::vector<int> devset_snapshot() {
   return g_devset;
 }
 
-// a cell / range / worker body run so that nothing is thrown out of a host thread or across the C ABI (std::bad_alloc from a
-// staging vector, a std::system_error from a lock): the unit fails as a device error
-template <class Fn>
-void run_guarded(int& rc, Fn&& fn) noexcept {
-  try {
-    fn();
-  } catch (...) {
-    rc = ZK_ERR_DEVICE;
+// the device set, or the calling thread's current device when none was given
+int devset_or_current(std::vector<int>* devs) {
+  *devs = devset_snapshot();
+  if (devs->empty()) {
+    int cur = 0;
+    ZK_HIP(hipGetDevice(&cur));
+    devs->push_back(cur);
   }
+  return ZK_OK;
 }
 
-
-// bases consumed by exponents [0, i) of a planned call (prefix popcount of the density map; i itself under FullDensity)
-uint64_t density_rank(const DensityPlan& P, const uint32_t* density, uint64_t i) {
-  if (density == nullptr || i == 0) return density == nullptr ? i : 0;
-  const uint64_t w = i >> 5;
-  if (w >= P.prefix.size()) {  // i == n on a word boundary past the last planned word
-    const uint64_t lw = P.prefix.size() - 1;
-    uint32_t v = density[lw];
-    if ((lw + 1) * 32 > P.n) v &= (P.n & 31) ? ((1u << (P.n & 31)) - 1u) : 0xffffffffu;
-    return P.prefix[lw] + (uint32_t)__builtin_popcount(v);
+// The fan-out of a call over its cells / ranges / workers: fn(0) .. fn(count - 1), unit 0 on the calling thread, every other unit on a host
+// thread of its own; the units whose thread could not be had run here afterwards, one after the other.  Returns the units' return codes.
+// Nothing is thrown out of a host thread or across the C ABI (std::bad_alloc from a staging vector, a std::system_error from a lock): the
+// unit fails as a device error.  The calling thread's current device is restored.
+template <class Fn>
+std::vector<int> fan_out(size_t count, Fn&& fn) {
+  std::vector<int> rcs(count, ZK_OK);
+  auto unit = [&](size_t i) noexcept {
+    try {
+      rcs[i] = fn(i);
+    } catch (...) {
+      rcs[i] = ZK_ERR_DEVICE;
+    }
+  };
+  DeviceGuard guard;
+  std::vector<std::thread> th;
+  size_t started = 1;
+  try {
+    for (; started < count; ++started) th.emplace_back([&, started] { unit(started); });
+  } catch (const std::exception&) {
+    // (no more host threads to be had -- nothing is thrown across the C ABI)
   }
-  uint64_t r = P.prefix[w];
-  if (i & 31) r += (uint32_t)__builtin_popcount(density[w] & ((1u << (i & 31)) - 1u));
-  return r;
+  if (count) unit(0);
+  for (size_t i = started; i < count; ++i) unit(i);
+  for (auto& t : th) t.join();
+  return rcs;
+}
+int first_error(const std::vector<int>& rcs) {
+  for (int rc : rcs)
+    if (rc != ZK_OK) return rc;
+  return ZK_OK;
 }
 
 template <int GROUP>
@@ -810,10 +864,8 @@ int msm_host_multi(const std::vector<int>& devs, const uint8_t* bases, size_t n_
                    size_t n_scalars, const uint32_t* density, size_t density_bits, uint64_t* out_xyz, const RecordLayout& L) {
   using J = typename std::conditional<GROUP == 1, G1Jacobian, G2Jacobian>::type;
   t_last_err_index = -1;
-  DensityPlan P;
-  int rc = plan_density(n_bases, base_offset, n_scalars, density, density_bits, &P);
-  if (rc) return rc;
-  const uint64_t n = P.eof_index >= 0 ? (uint64_t)P.eof_index : P.n;  // exponents before the first Eof
+  const DensityPlan P = plan_density(n_bases, base_offset, n_scalars, density, density_bits);
+  const uint64_t n = P.live();
   // ---- the plan: point ranges x window groups
   uint32_t pg = (uint32_t)devs.size(), wg = 1;
   if (const char* env = std::getenv("MI355ZK_MULTI_PLAN")) {
@@ -833,7 +885,6 @@ int msm_host_multi(const std::vector<int>& devs, const uint8_t* bases, size_t n_
     int dev = 0;
     uint64_t lo = 0, hi = 0;
     uint32_t wgi = 0;
-    int rc = ZK_OK;
     long long err = -1;
     J part;
   };
@@ -849,56 +900,45 @@ int msm_host_multi(const std::vector<int>& devs, const uint8_t* bases, size_t n_
       c.part = J::zero();
       cells.push_back(c);
     }
-  static const bool trace = std::getenv("MI355ZK_TRACE_HOST") != nullptr;
   const auto t0 = std::chrono::steady_clock::now();
   auto run_cell = [&](Cell& c) {
-    if (hipSetDevice(c.dev) != hipSuccess) { c.rc = ZK_ERR_DEVICE; return; }
+    if (hipSetDevice(c.dev) != hipSuccess) return ZK_ERR_DEVICE;
     // The cell sees only the SLICE of the base vector its exponents consume -- [boff, boff + used) -- as a vector of its own: that is what
     // its device allocates, uploads and (inside a pinned vector) keeps: 2^26 G1 points on 8 devices are 512 MiB per device, not 4 GiB
     // (SURVEY 8e).  The ranges end before the first exponent without a base (the Eof is planned above for the whole call), so the slice
     // holds every base the cell asks for.
     const size_t hs = L.host_stride(GROUP);  // bytes per host record
-    const uint64_t boff = base_offset + density_rank(P, density, c.lo);
-    const uint64_t used = density_rank(P, density, c.hi) - density_rank(P, density, c.lo);
+    const uint64_t boff = base_offset + P.rank(c.lo);
+    const uint64_t used = P.rank(c.hi) - P.rank(c.lo);
     struct ParentScope {
       explicit ParentScope(const void* p) { t_bases_parent = p; }
       ~ParentScope() { t_bases_parent = nullptr; }
     } parent_scope(bases);
-    c.rc = msm_host_run<GROUP>(bases + boff * hs, used, 0, scalars + c.lo * 4, c.hi - c.lo, density ? density + (c.lo >> 5) : nullptr,
-                               density ? c.hi - c.lo : 0, reinterpret_cast<uint64_t*>(&c.part), L, wg, c.wgi);
+    const int rc = msm_host_run<GROUP>(bases + boff * hs, used, 0, scalars + c.lo * 4, c.hi - c.lo, density ? density + (c.lo >> 5) : nullptr,
+                                       density ? c.hi - c.lo : 0, reinterpret_cast<uint64_t*>(&c.part), L, wg, c.wgi);
     c.err = t_last_err_index;
-    if (trace)
+    if (trace_host())
       std::fprintf(stderr, "[mi355zk] multi: cell [%llu, %llu) window group %u/%u on device %d: rc %d at %.2f ms\n", (unsigned long long)c.lo,
-                   (unsigned long long)c.hi, c.wgi, wg, c.dev, c.rc,
-                   std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+                   (unsigned long long)c.hi, c.wgi, wg, c.dev, rc, ms_since(t0));
+    return rc;
   };
-  {
-    DeviceGuard guard;
-    std::vector<std::thread> th;
-    size_t started = 1;
-    try {
-      for (; started < cells.size(); ++started) th.emplace_back([&, started] { run_guarded(cells[started].rc, [&] { run_cell(cells[started]); }); });
-    } catch (const std::exception&) {
-      // (no more host threads to be had: the cells that did not get one run here, one after the other -- nothing is thrown across the C ABI)
-    }
-    if (!cells.empty()) run_guarded(cells[0].rc, [&] { run_cell(cells[0]); });
-    for (size_t i = started; i < cells.size(); ++i) run_guarded(cells[i].rc, [&] { run_cell(cells[i]); });
-    for (auto& t : th) t.join();
-  }
+  const std::vector<int> rcs = fan_out(cells.size(), [&](size_t i) { return run_cell(cells[i]); });
   // ---- the join.  Device failures first, then a non-canonical exponent (bad arguments: the single-device call reports it before
   // anything else too), then the Source errors by global exponent index.
   J total = J::zero();
   long long bad_idx = -1, ident_idx = -1;
-  for (Cell& c : cells) {
-    if (c.rc < 0) return c.rc;
-    if (c.rc == ZK_ERR_BAD_ARGS) {
+  for (size_t i = 0; i < cells.size(); ++i) {
+    const Cell& c = cells[i];
+    const int rc = rcs[i];
+    if (rc < 0) return rc;
+    if (rc == ZK_ERR_BAD_ARGS) {
       const long long g = c.err >= 0 ? c.err + (long long)c.lo : -1;
       if (bad_idx < 0 || (g >= 0 && g < bad_idx)) bad_idx = g >= 0 ? g : bad_idx;
       if (g < 0) { t_last_err_index = -1; return ZK_ERR_BAD_ARGS; }
-    } else if (c.rc == ZK_ERR_UNEXPECTED_IDENTITY) {
+    } else if (rc == ZK_ERR_UNEXPECTED_IDENTITY) {
       const long long g = c.err + (long long)c.lo;
       if (ident_idx < 0 || g < ident_idx) ident_idx = g;
-    } else if (c.rc != ZK_OK) {
+    } else if (rc != ZK_OK) {
       return ZK_ERR_DEVICE;  // (a cell never reports Eof: the ranges end before the first exponent without a base)
     }
   }
@@ -914,9 +954,10 @@ int msm_host_multi(const std::vector<int>& devs, const uint8_t* bases, size_t n_
 template <int GROUP>
 int msm_host_entry(const uint8_t* bases, size_t n_bases, size_t base_offset, const uint64_t* scalars, size_t n_scalars,
                    const uint32_t* density, size_t density_bits, uint64_t* out_xyz, const RecordLayout& L) {
+  // (the raw set, not devset_or_current: none or one device means "whole, on the CALLER's current device", which need not be the set's)
   const std::vector<int> devs = devset_snapshot();
   if (devs.size() <= 1) return msm_host_run<GROUP>(bases, n_bases, base_offset, scalars, n_scalars, density, density_bits, out_xyz, L);
-  if (!out_xyz || (n_scalars && !scalars) || (n_bases && !bases) || n_bases >= (1ull << 31) || n_scalars >= (1ull << 31)) {
+  if (!msm_host_args_ok(bases, n_bases, scalars, n_scalars, out_xyz)) {
     t_last_err_index = -1;
     return ZK_ERR_BAD_ARGS;
   }
@@ -952,53 +993,41 @@ int batch_exp_host(uint8_t* out, const uint8_t* bases, const uint64_t* scalars, 
   if (n == 0) return ZK_OK;
   if (n >= (1ull << 31)) return ZK_ERR_BAD_ARGS;
   constexpr size_t rec = sizeof(Affine<F>);
-  std::vector<int> devs = devset_snapshot();
-  if (devs.empty()) {
-    int cur = 0;
-    ZK_HIP(hipGetDevice(&cur));
-    devs.push_back(cur);
-  }
+  std::vector<int> devs;
+  if (int rc = devset_or_current(&devs)) return rc;
   size_t parts = devs.size();
   while (parts > 1 && n / parts < 1024) --parts;
-  std::vector<int> rcs(parts, ZK_OK);
-  auto run_range = [&](size_t d) {
+  auto run_range = [&](size_t d) -> int {
     const size_t lo = n * d / parts, hi = n * (d + 1) / parts;
-    if (hipSetDevice(devs[d]) != hipSuccess) { rcs[d] = ZK_ERR_DEVICE; return; }
-    StageLease stage_lease;
-    HostStage* S = host_stage(devs[d], &stage_lease);
-    if (S == nullptr) { rcs[d] = ZK_ERR_DEVICE; return; }
+    if (hipSetDevice(devs[d]) != hipSuccess) return ZK_ERR_DEVICE;
     // pieces of 2^18 points, double-buffered
     const size_t piece = (size_t)1 << 18;
     const size_t m_max = hi - lo < piece ? hi - lo : piece;
     const size_t in_bytes = (m_max * rec + 255) & ~(size_t)255;
     const size_t sc_bytes = same_scalar ? 256 : ((m_max * 32 + 255) & ~(size_t)255);
-    DensityPool::Lease buf;   // (the grow-only device buffer pool of the host-buffer entry points)
-    int rc = buf.acquire(devs[d], 4 * in_bytes + 2 * sc_bytes, S->compute);
-    if (rc) { rcs[d] = rc; return; }
-    char* base = (char*)buf.b->p;
+    Events ev(4);   // (declared before the lease: destroyed after both streams are idle)
+    hipEvent_t* up = &ev.e[0];
+    hipEvent_t* done = &ev.e[2];
+    CallLease lease;
+    int rc = lease.open(devs[d], 4 * in_bytes + 2 * sc_bytes);
+    if (rc) return rc;
+    HostStage* S = lease.S;
+    char* base = (char*)lease.buf;
     char* d_in[2] = {base, base + in_bytes};
     char* d_out[2] = {base + 2 * in_bytes, base + 3 * in_bytes};
     char* d_sc[2] = {base + 4 * in_bytes, base + 4 * in_bytes + sc_bytes};
-    hipEvent_t up[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr};
-    auto cleanup = [&] {
-      (void)hipStreamSynchronize(S->copy);
-      (void)hipStreamSynchronize(S->compute);
-      for (int k = 0; k < 2; ++k) { if (up[k]) (void)hipEventDestroy(up[k]); if (done[k]) (void)hipEventDestroy(done[k]); }
-    };
     auto fail = [&](hipError_t e) {
       std::fprintf(stderr, "[mi355zk] batch_exp (host buffers): HIP error %d (%s)\n", (int)e, hipGetErrorString(e));
-      rcs[d] = ZK_ERR_DEVICE;
-      cleanup();
+      return ZK_ERR_DEVICE;
     };
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 2; ++k)
-      if ((e = hipEventCreateWithFlags(&up[k], hipEventDisableTiming)) != hipSuccess || (e = hipEventCreateWithFlags(&done[k], hipEventDisableTiming)) != hipSuccess) return fail(e);
+    hipError_t e = ev.create();
+    if (e != hipSuccess) return fail(e);
     if (same_scalar && (e = hipMemcpyAsync(d_sc[0], scalars, 32, hipMemcpyHostToDevice, S->copy)) != hipSuccess) return fail(e);
     // ONE host thread keeps the device busy although copies from / to PAGEABLE host memory block it: the kernels of piece i + 1 are
     // always queued before the thread waits for piece i's download, and piece i + 2 is uploaded (into the buffer piece i's kernels
     // have finished with: its download has just returned) while piece i + 1 computes.
     const size_t n_pieces = (hi - lo + piece - 1) / piece;
-    auto upload_and_launch = [&](size_t i) -> bool {
+    auto upload_and_launch = [&](size_t i) -> bool {   // false: rc, or else e, says why
       const size_t p0 = lo + i * piece, m = hi - p0 < piece ? hi - p0 : piece;
       const int k = (int)(i & 1);
       if ((e = hipMemcpyAsync(d_in[k], bases + p0 * rec, m * rec, hipMemcpyHostToDevice, S->copy)) != hipSuccess) return false;
@@ -1008,38 +1037,20 @@ int batch_exp_host(uint8_t* out, const uint8_t* bases, const uint64_t* scalars, 
       if (rc) return false;
       return (e = hipEventRecord(done[k], S->compute)) == hipSuccess;
     };
-    auto bail = [&] {
-      if (rc) { rcs[d] = rc; cleanup(); }
-      else fail(e);
-    };
     for (size_t i = 0; i < 2 && i < n_pieces; ++i)
-      if (!upload_and_launch(i)) return bail();
+      if (!upload_and_launch(i)) return rc ? rc : fail(e);
     for (size_t i = 0; i < n_pieces; ++i) {
       const size_t p0 = lo + i * piece, m = hi - p0 < piece ? hi - p0 : piece;
       const int k = (int)(i & 1);
       if ((e = hipStreamWaitEvent(S->copy, done[k], 0)) != hipSuccess) return fail(e);
       if ((e = hipMemcpyAsync(out + p0 * rec, d_out[k], m * rec, hipMemcpyDeviceToHost, S->copy)) != hipSuccess) return fail(e);
       if ((e = hipStreamSynchronize(S->copy)) != hipSuccess) return fail(e);   // piece i is on the host; its buffers are free
-      if (i + 2 < n_pieces && !upload_and_launch(i + 2)) return bail();
+      if (i + 2 < n_pieces && !upload_and_launch(i + 2)) return rc ? rc : fail(e);
     }
     if ((e = hipStreamSynchronize(S->compute)) != hipSuccess) return fail(e);
-    cleanup();
+    return ZK_OK;
   };
-  {
-    DeviceGuard guard;
-    std::vector<std::thread> th;
-    size_t started = 1;
-    try {
-      for (; started < parts; ++started) th.emplace_back([&, started] { run_guarded(rcs[started], [&] { run_range(started); }); });
-    } catch (const std::exception&) {
-    }
-    run_guarded(rcs[0], [&] { run_range(0); });
-    for (size_t d = started; d < parts; ++d) run_guarded(rcs[d], [&] { run_range(d); });
-    for (auto& t : th) t.join();
-  }
-  for (int rc : rcs)
-    if (rc != ZK_OK) return rc;
-  return ZK_OK;
+  return first_error(fan_out(parts, run_range));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1056,12 +1067,8 @@ int dense_host(const uint8_t* v1, const uint8_t* v2, const uint64_t* rho, size_t
   if (!out_s || (v2 && !out_sx) || (n && (!v1 || !rho)) || n >= (1ull << 31)) return ZK_ERR_BAD_ARGS;
   J total = J::zero(), total2 = J::zero();
   if (n > 0) {
-    std::vector<int> devs = devset_snapshot();
-    if (devs.empty()) {
-      int cur = 0;
-      ZK_HIP(hipGetDevice(&cur));
-      devs.push_back(cur);
-    }
+    std::vector<int> devs;
+    if (int rc = devset_or_current(&devs)) return rc;
     size_t piece = (size_t)1 << 22;
     if (const char* env = std::getenv("MI355ZK_DENSE_PIECE_TEST")) {   // (test hook, read per call: points per piece, so that the cut can be held against the oracle)
       const size_t v = (size_t)std::strtoull(env, nullptr, 10);
@@ -1070,22 +1077,22 @@ int dense_host(const uint8_t* v1, const uint8_t* v2, const uint64_t* rho, size_t
     const size_t n_pieces = (n + piece - 1) / piece;
     size_t workers = 2 * devs.size();
     if (workers > n_pieces) workers = n_pieces;
-    struct Part { int rc = ZK_OK; J s, sx; };
+    struct Part { J s, sx; };
     std::vector<Part> parts(workers);
     for (auto& pt : parts) { pt.s = J::zero(); pt.sx = J::zero(); }
     std::atomic<size_t> next{0};
-    auto work = [&](size_t wk) {
+    // (a worker takes pieces until none is left: one that got no thread and runs late, on the calling thread, finds nothing to do)
+    auto work = [&](size_t wk) -> int {
       Part& P = parts[wk];
       const int dev = devs[wk % devs.size()];
-      if (hipSetDevice(dev) != hipSuccess) { P.rc = ZK_ERR_DEVICE; return; }
-      StageLease stage_lease;
-      HostStage* S = host_stage(dev, &stage_lease);
-      if (S == nullptr) { P.rc = ZK_ERR_DEVICE; return; }
+      if (next.load() >= n_pieces) return ZK_OK;   // (run late: no stage, no buffer for nothing)
+      if (hipSetDevice(dev) != hipSuccess) return ZK_ERR_DEVICE;
       const size_t m_max = n < piece ? n : piece;
       const size_t vb = ((m_max + 16) * rec + 255) & ~(size_t)255;
-      DensityPool::Lease buf;
-      if (int rc = buf.acquire(dev, (v2 ? 2 : 1) * vb + m_max * 32, S->compute)) { P.rc = rc; return; }
-      char* d_v1 = (char*)buf.b->p;
+      CallLease lease;
+      if (int rc = lease.open(dev, (v2 ? 2 : 1) * vb + m_max * 32)) return rc;
+      HostStage* S = lease.S;
+      char* d_v1 = (char*)lease.buf;
       // power_pairs (utils.rs:133-135) is merge_pairs(v[0 .. n-1], v[1 .. n]): the two vectors are ONE array seen at two offsets, and
       // uploading it twice would double the PCIe traffic of a call the link already bounds -- a v2 that starts `shift` (<= 16)
       // records into v1 shares v1's upload
@@ -1105,30 +1112,19 @@ int dense_host(const uint8_t* v1, const uint8_t* v2, const uint64_t* rho, size_t
         if (e == hipSuccess) e = hipMemcpyAsync(d_rho, rho + p0 * 4, m * 32, hipMemcpyHostToDevice, S->compute);
         if (e != hipSuccess) {
           std::fprintf(stderr, "[mi355zk] dense multiexp (host buffers): HIP error %d (%s)\n", (int)e, hipGetErrorString(e));
-          P.rc = ZK_ERR_DEVICE;
-          return;
+          return ZK_ERR_DEVICE;
         }
         J a = J::zero(), b = J::zero();
         const int rc = GROUP == 1 ? msm_g1_dense_device(d_v1, d_v2, d_rho, m, S->compute, reinterpret_cast<uint64_t*>(&a), v2 ? reinterpret_cast<uint64_t*>(&b) : nullptr)
                                   : msm_g2_dense_device(d_v1, d_v2, d_rho, m, S->compute, reinterpret_cast<uint64_t*>(&a), v2 ? reinterpret_cast<uint64_t*>(&b) : nullptr);
-        if (rc != ZK_OK) { P.rc = rc; return; }
+        if (rc != ZK_OK) return rc;
         jac_add(P.s, a);
         if (v2) jac_add(P.sx, b);
       }
+      return ZK_OK;
     };
-    {
-      DeviceGuard guard;
-      std::vector<std::thread> th;
-      size_t started = 1;
-      try {
-        for (; started < workers; ++started) th.emplace_back([&, started] { run_guarded(parts[started].rc, [&] { work(started); }); });
-      } catch (const std::exception&) {
-      }
-      run_guarded(parts[0].rc, [&] { work(0); });   // (a worker takes pieces until none is left: the ones that got no thread are covered by the others)
-      for (auto& t : th) t.join();
-    }
+    if (int rc = first_error(fan_out(workers, work))) return rc;
     for (auto& pt : parts) {
-      if (pt.rc != ZK_OK) return pt.rc;
       jac_add(total, pt.s);
       if (v2) jac_add(total2, pt.sx);
     }
@@ -1149,13 +1145,11 @@ int ntt_host(uint64_t* a, uint32_t log_n, int op, const uint64_t* omega) {
   const size_t bytes = (size_t)32 << log_n;
   int dev = 0;
   ZK_HIP(hipGetDevice(&dev));
-  StageLease stage_lease;
-  HostStage* S = host_stage(dev, &stage_lease);
-  if (S == nullptr) return ZK_ERR_DEVICE;
-  DensityPool::Lease buf;   // (a grow-only device buffer pool; the lease synchronises the stream before the buffer is handed on)
-  int rc = buf.acquire(dev, bytes, S->compute);
+  CallLease lease;   // (the lease synchronises the streams before the buffer is handed on)
+  int rc = lease.open(dev, bytes);
   if (rc) return rc;
-  void* d = buf.b->p;
+  HostStage* S = lease.S;
+  void* d = lease.buf;
   ZK_HIP(hipMemcpyAsync(d, a, bytes, hipMemcpyHostToDevice, S->compute));
   if (omega) {
     Fr w;
@@ -1185,26 +1179,13 @@ int h_poly_host(uint64_t* h, const uint64_t* a, const uint64_t* b, const uint64_
   const size_t n = (size_t)1 << log_n, bytes = n * 32;
   int dev = 0;
   ZK_HIP(hipGetDevice(&dev));
-  StageLease stage_lease;
-  HostStage* S = host_stage(dev, &stage_lease);
-  if (S == nullptr) return ZK_ERR_DEVICE;
-  DensityPool::Lease buf;
-  int rc = buf.acquire(dev, 3 * bytes, S->compute);
+  Events ev(3);   // (declared before the lease: destroyed after both streams are idle)
+  CallLease lease;
+  int rc = lease.open(dev, 3 * bytes);
   if (rc) return rc;
-  struct Events {
-    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-    HostStage* S;
-    ~Events() {
-      // an error path may leave copies queued into the leased buffer: both streams are idle before it goes back to the pool
-      (void)hipStreamSynchronize(S->copy);
-      (void)hipStreamSynchronize(S->compute);
-      for (hipEvent_t x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } ev;
-  ev.S = S;
-  for (hipEvent_t& x : ev.e) ZK_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-  Fr* d[3] = {(Fr*)buf.b->p, (Fr*)buf.b->p + n, (Fr*)buf.b->p + 2 * n};
+  HostStage* S = lease.S;
+  ZK_HIP(ev.create());
+  Fr* d[3] = {(Fr*)lease.buf, (Fr*)lease.buf + n, (Fr*)lease.buf + 2 * n};
   const uint64_t* src[3] = {a, b, c};
   for (int k = 0; k < 3; ++k) {
     if (len < n) ZK_HIP(hipMemsetAsync(d[k] + len, 0, (n - len) * 32, S->copy));   // from_coeffs: resize(m, zero) (domain.rs:80-82)
@@ -1212,8 +1193,8 @@ int h_poly_host(uint64_t* h, const uint64_t* a, const uint64_t* b, const uint64_
       const size_t m = len - lo < H_POLY_PIECE ? len - lo : H_POLY_PIECE;
       ZK_HIP(hipMemcpyAsync(d[k] + lo, src[k] + lo * 4, m * 32, hipMemcpyHostToDevice, S->copy));
     }
-    ZK_HIP(hipEventRecord(ev.e[k], S->copy));
-    ZK_HIP(hipStreamWaitEvent(S->compute, ev.e[k], 0));
+    ZK_HIP(hipEventRecord(ev[k], S->copy));
+    ZK_HIP(hipStreamWaitEvent(S->compute, ev[k], 0));
 #ifndef ZK_H_POLY_HOST_BATCHED
     rc = domain_op_dev(d[k], log_n, MI355ZK_OP_IFFT, S->compute);
     if (rc == ZK_OK) rc = domain_op_dev(d[k], log_n, MI355ZK_OP_COSET_FFT, S->compute);
@@ -1310,12 +1291,8 @@ int sparse_matvec_host(uint8_t* out, const uint8_t* bases, size_t n_bases, const
   if (!row_ptr || (n_rows && !out) || (nnz && (!bases || !col || !coeffs)) || n_rows >= (1ull << 31) || nnz >= (1ull << 31) || n_bases >= (1ull << 31)) return ZK_ERR_BAD_ARGS;
   if (n_rows == 0) return ZK_OK;
   if (row_ptr[0] != 0 || row_ptr[n_rows] != nnz) return ZK_ERR_BAD_ARGS;
-  std::vector<int> devs = devset_snapshot();
-  if (devs.empty()) {
-    int cur = 0;
-    ZK_HIP(hipGetDevice(&cur));
-    devs.push_back(cur);
-  }
+  std::vector<int> devs;
+  if (int rc = devset_or_current(&devs)) return rc;
   size_t parts = devs.size();
   while (parts > 1 && n_rows / parts < 128) --parts;
   // cuts of equal WEIGHT (rows + terms: a row costs a normalisation, a term an addition chain), found by one walk over row_ptr -- the
@@ -1328,28 +1305,25 @@ int sparse_matvec_host(uint8_t* out, const uint8_t* bases, size_t n_bases, const
     for (size_t r = 0; r < n_rows && d < parts; ++r)
       while (d < parts && r + (size_t)row_ptr[r] >= weight * d / parts) cut[d++] = r;
   }
-  std::vector<int> rcs(parts, ZK_OK);
-  auto run_range = [&](size_t d) {
+  auto run_range = [&](size_t d) -> int {
     const size_t r0 = cut[d], r1 = cut[d + 1];
-    if (r1 == r0) return;
+    if (r1 == r0) return ZK_OK;
     const uint32_t t0 = row_ptr[r0], t1 = row_ptr[r1];
-    if (t1 < t0) { rcs[d] = ZK_ERR_BAD_ARGS; return; }
+    if (t1 < t0) return ZK_ERR_BAD_ARGS;
     const size_t rows = r1 - r0, terms = t1 - t0;
-    if (hipSetDevice(devs[d]) != hipSuccess) { rcs[d] = ZK_ERR_DEVICE; return; }
-    StageLease stage_lease;
-    HostStage* S = host_stage(devs[d], &stage_lease);
-    if (S == nullptr) { rcs[d] = ZK_ERR_DEVICE; return; }
+    if (hipSetDevice(devs[d]) != hipSuccess) return ZK_ERR_DEVICE;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t o_bases = 0, o_out = o_bases + al((n_bases ? n_bases : 1) * rec), o_rp = o_out + al(rows * rec), o_col = o_rp + al((rows + 1) * 4),
                  o_cf = o_col + al((terms ? terms : 1) * 4), o_scr = o_cf + al((terms ? terms : 1) * 32),
                  scr_bytes = al((terms ? terms : 1) * rec) + 256 + al(n_bases), total = o_scr + scr_bytes;
-    DensityPool::Lease buf;
-    if (int rc = buf.acquire(devs[d], total, S->compute)) { rcs[d] = rc; return; }
-    char* base = (char*)buf.b->p;
+    CallLease lease;
+    if (int rc = lease.open(devs[d], total)) return rc;
+    HostStage* S = lease.S;
+    char* base = (char*)lease.buf;
     std::vector<uint32_t> rp(rows + 1);
     for (size_t r = 0; r <= rows; ++r) {
       const uint32_t v = row_ptr[r0 + r];
-      if (v < t0 || v > t1) { rcs[d] = ZK_ERR_BAD_ARGS; return; }   // (monotone inside the range is checked on the device)
+      if (v < t0 || v > t1) return ZK_ERR_BAD_ARGS;   // (monotone inside the range is checked on the device)
       rp[r] = v - t0;
     }
     hipError_t e = hipSuccess;
@@ -1358,29 +1332,15 @@ int sparse_matvec_host(uint8_t* out, const uint8_t* bases, size_t n_bases, const
     if (e == hipSuccess && terms) e = hipMemcpyAsync(base + o_col, col + t0, terms * 4, hipMemcpyHostToDevice, S->compute);
     if (e == hipSuccess && terms) e = hipMemcpyAsync(base + o_cf, coeffs + (size_t)t0 * 4, terms * 32, hipMemcpyHostToDevice, S->compute);
     if (e == hipSuccess) e = hipStreamSynchronize(S->compute);   // (rp is a local vector)
-    if (e != hipSuccess) { rcs[d] = ZK_ERR_DEVICE; return; }
-    int rc = sparse_matvec<F>(base + o_out, base + o_bases, n_bases, (const uint32_t*)(base + o_rp), (const uint32_t*)(base + o_col), base + o_cf, rows, terms,
-                              (void*)S->compute, group, g2_trusted, base + o_scr, scr_bytes);
-    if (rc != ZK_OK) { rcs[d] = rc; return; }
+    if (e != hipSuccess) return ZK_ERR_DEVICE;
+    const int rc = sparse_matvec<F>(base + o_out, base + o_bases, n_bases, (const uint32_t*)(base + o_rp), (const uint32_t*)(base + o_col), base + o_cf, rows, terms,
+                                    (void*)S->compute, group, g2_trusted, base + o_scr, scr_bytes);
+    if (rc != ZK_OK) return rc;
     e = hipMemcpyAsync(out + r0 * rec, base + o_out, rows * rec, hipMemcpyDeviceToHost, S->compute);
     if (e == hipSuccess) e = hipStreamSynchronize(S->compute);
-    if (e != hipSuccess) rcs[d] = ZK_ERR_DEVICE;
+    return e == hipSuccess ? ZK_OK : ZK_ERR_DEVICE;
   };
-  {
-    DeviceGuard guard;
-    std::vector<std::thread> th;
-    size_t started = 1;
-    try {
-      for (; started < parts; ++started) th.emplace_back([&, started] { run_guarded(rcs[started], [&] { run_range(started); }); });
-    } catch (const std::exception&) {
-    }
-    run_guarded(rcs[0], [&] { run_range(0); });
-    for (size_t d = started; d < parts; ++d) run_guarded(rcs[d], [&] { run_range(d); });
-    for (auto& t : th) t.join();
-  }
-  for (int rc : rcs)
-    if (rc != ZK_OK) return rc;
-  return ZK_OK;
+  return first_error(fan_out(parts, run_range));
 }
 
 // ---- what api.hip's lifecycle / cache wrappers need of the state above

@@ -824,6 +824,42 @@ def test_streamed_chunks_against_the_oracle(zk, worker, group, monkeypatch):
     assert e.value.kind == zk.SynthesisError.UNEXPECTED_IDENTITY and e.value.index == target
 
 
+def test_streamed_chunks_ending_on_a_density_word_boundary(zk, worker, monkeypatch):
+    """The chunked host-buffer call whose LAST chunk ends on a density-word boundary: 2048 exponents in chunks of 512, unpinned bases
+    (they travel with the chunks, so the copy thread asks for the bases consumed by exponents [0, 2048) -- the rank of an index one
+    past the last planned density word).  Density ~0.7 with the last bit of the last word set; against the CPU oracle.  An identity
+    base under that last bit and a vector one base short both report exponent 2047."""
+    monkeypatch.setenv("MI355ZK_HOST_CHUNK_TEST", "512")
+    G = O.G1
+    n, off = 2048, 4
+    rng = np.random.default_rng(2750)
+    bits = rng.random(n) < 0.7
+    bits[n - 1] = True
+    used = int(bits.sum())
+    bases = inputs.bases_progression_cpu(1, used + off, seed=2751)
+    scalars = inputs.random_scalars(n, seed=2752)
+    scalars[::19] = 0
+    assert scalars[n - 1].any()
+    dens = GU.density_words(bits)
+    rc, want = G.multiexp(bases, scalars, density=dens, density_bits=n, base_offset=off, threads=4)
+    assert rc == 0
+    dm = zk.DensityTracker.from_bools(bits)
+    got = zk.multiexp(worker, (bases, off), dm, scalars).wait()
+    assert np.array_equal(G.to_affine(got), G.to_affine(want))
+    # an identity base under the last set bit of the last word
+    bad = bases.copy()
+    bad[off + used - 1] = 0
+    rc, _ = G.multiexp(bad, scalars, density=dens, density_bits=n, base_offset=off)
+    assert rc == 1
+    with pytest.raises(zk.SynthesisError) as e:
+        zk.multiexp(worker, (bad, off), dm, scalars).wait()
+    assert e.value.kind == zk.SynthesisError.UNEXPECTED_IDENTITY and e.value.index == n - 1
+    # one base short: Eof at that exponent
+    with pytest.raises(zk.SynthesisError) as e:
+        zk.multiexp(worker, (bases[:used + off - 1].copy(), off), dm, scalars).wait()
+    assert e.value.kind == zk.SynthesisError.IO_UNEXPECTED_EOF and e.value.index == n - 1
+
+
 def test_host_entry_streamed_g2_and_heavy_buckets_in_later_chunks(zk, worker):
     """The streamed host-buffer call carries ONE bucket array across its chunks (msm_accumulate_kernel<.., CARRY>,
     msm_heavy_combine_kernel with carry): G2 at 2^23 points (four chunks), and G1 with prover-like exponents whose byte-valued
