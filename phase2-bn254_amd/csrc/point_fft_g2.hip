@@ -12,6 +12,8 @@
 // out-of-line calls with these operands go through scratch and crawl).
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
+
 #include "../../include/mi355zk.h"
 #include "curveu.hpp"
 #include "glv.hpp"
@@ -189,13 +191,22 @@ __global__ void pfft2_twiddle_kernel(uint32_t* tw, Fr omega, uint64_t count) {
   for (int l = 0; l < 8; ++l) tw[e * 8 + l] = c.l[l];
 }
 
+// lanes per launch of a stage: the built-in limit, or (test hook, read on every call) MI355ZK_PFFT_CHUNK_TEST = a decimal count >= 1 below it, of ANY
+// value -- the launch loop, a second launch over the same table and a ragged last launch then run at sizes the CPU oracle checks record by record
+uint64_t pfft_lanes_per_launch(uint64_t built_in) {
+  const char* env_test = std::getenv("MI355ZK_PFFT_CHUNK_TEST");
+  const uint64_t v = env_test ? (uint64_t)std::strtoull(env_test, nullptr, 10) : 0;
+  return v >= 1 && v < built_in ? v : built_in;
+}
+
 }  // namespace
 
 // d_points: 2^log_n affine raw G2 records (128 B), in place.  scale: every output is multiplied by scale_canon (ifft: m^-1).
 int point_fft_g2(void* d_points, uint32_t log_n, const Fr& omega, bool scale, const Fr& scale_canon, hipStream_t st, bool trusted_subgroup) {
   const uint64_t n = 1ull << log_n;
   const uint64_t lanes_max = scale ? n : (n >= 2 ? n / 2 : 1);
-  const uint64_t chunk = lanes_max < (1ull << 19) ? lanes_max : (1ull << 19);  // table: 8 x 368 B per lane
+  const uint64_t limit = pfft_lanes_per_launch(1ull << 19);
+  const uint64_t chunk = lanes_max < limit ? lanes_max : limit;  // table: 8 x 368 B per lane
   char* buf = nullptr;
   const size_t o_work = 0, o_tw = o_work + ((n * sizeof(J2) + 255) & ~(size_t)255), o_z = o_tw + (((n / 2 + 1) * 32 + 255) & ~(size_t)255),
                o_tab = o_z + ((n * sizeof(Fq2) + 255) & ~(size_t)255), total = o_tab + 8 * chunk * sizeof(JacTabU2);
