@@ -288,6 +288,30 @@ int mi355zk_bn254_fr_sub_assign_dev(void *d_a, const void *d_b, size_t n, void *
 /* out[i] = into_repr(in[i]): Montgomery Fr -> canonical FrRepr (scalars_into_representations / field_elements_into_representations,
  * prover.rs:89-129) as a standalone pass; d_out may alias d_in.  (The multiexp can take Montgomery scalars directly: msm_ex_dev.) */
 int mi355zk_bn254_fr_into_repr_dev(void *d_out, const void *d_in, size_t n, void *stream);
+/* out[i] = in[i] * 2^256 mod r: canonical FrRepr -> Montgomery Fr (the inverse of mi355zk_bn254_fr_into_repr_dev); in < r, unchecked; may alias. */
+int mi355zk_bn254_fr_from_repr_dev(void *d_out, const void *d_in, size_t n, void *stream);
+/* ---- sparse matrix x vector over Fr (csrc/r1cs.hip): the evaluation of an R1CS on a witness, a[i] = sum_t coeff_t * w[var_t] over the terms
+ * of constraint i (ProvingAssignment::enforce / eval, groth16/prover.rs:50-87), with the matrix resident on the device in CSR form.
+ * out[r] = sum_{t = row_ptr[r]}^{row_ptr[r+1]-1} coeffs[coeff_id[t]] * x[col[t]],  r < n_rows   (all Montgomery Fr, canonical < r)
+ * row_ptr: u32[n_rows + 1] from 0 to nnz, col: u32[nnz] (< n_x), coeff_id: u32[nnz] (< n_coeffs), coeffs: n_coeffs x 32 B, x: n_x x 32 B;
+ * all device pointers; an empty row gives 0.  Asynchronous on `stream`, no host synchronisation.
+ * The coefficients go through a table of DISTINCT values (a circuit has few: 1, -1, powers of two), 4 B per term instead of 32; a caller
+ * without such a table passes coeff_id[t] = t.  Every term is multiplied (the reference skips the product by one: same field element), and
+ * every step returns the canonical residue, so the result does not depend on the order of the summation.
+ * Operand range: as for mul_assign / sub_assign above -- canonical Montgomery Fr, unchecked; an element >= r of x or coeffs makes the rows
+ * that use it UNDEFINED, the call still returns 0 and the other rows are unaffected.
+ * Index range: the call never reads or writes outside the arrays it was given, WHATEVER the index arrays hold -- every row's term range is
+ * clamped to [0, nnz), and a term whose col >= n_x or coeff_id >= n_coeffs contributes nothing.  For such a structure the results are
+ * unspecified, the call still returns 0 and nothing faults; it is not reported here, because that would cost a host synchronisation per
+ * call: mi355zk_bn254_fr_sparse_matvec_check_dev below validates a matrix ONCE, synchronously.
+ * 3 (before any device work) = a NULL pointer with a non-zero count; n_rows, nnz, n_x or n_coeffs >= 2^32; d_out == d_x.
+ * n_rows == 0 succeeds and launches nothing. */
+int mi355zk_bn254_fr_sparse_matvec_dev(void *d_out, const uint32_t *d_row_ptr, const uint32_t *d_col, const uint32_t *d_coeff_id,
+                                       const void *d_coeffs, size_t n_coeffs, const void *d_x, size_t n_x, size_t n_rows, size_t nnz, void *stream);
+/* Synchronous structural check, once per matrix: 0, or 3 if row_ptr is not monotone from 0 to nnz, a col >= n_x or a coeff_id >= n_coeffs
+ * (and for the argument errors of the evaluating call, before any device work). */
+int mi355zk_bn254_fr_sparse_matvec_check_dev(const uint32_t *d_row_ptr, const uint32_t *d_col, const uint32_t *d_coeff_id,
+                                             size_t n_coeffs, size_t n_x, size_t n_rows, size_t nnz, void *stream);
 /* EvaluationDomain::divide_by_z_on_coset (domain.rs:207-234): a[i] *= (g^m - 1)^-1 with m = 2^log_n and g = 7 the multiplicative
  * generator (z(tau) = tau^m - 1, domain.rs:207-212) -- the division step of the prover's H polynomial (prover.rs:217-241), so that
  * the whole ifft / coset_fft / mul / sub / divide / icoset_fft pipeline stays in HBM.  Asynchronous on `stream`. */

@@ -260,6 +260,164 @@ def prepare_prover(circuit: CircomCircuit, device):
                                      DensityTracker.from_bools(b_in), DensityTracker.from_bools(b_aux))
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# the same evaluation with the circuit COMPILED ONCE: what depends on the circuit and not on the witness (the term lists as one CSR
+# matrix on the device, the density maps) is built by compile_circuit; every witness then costs one upload and two kernels
+# (mi355zk_bn254_fr_from_repr_dev, mi355zk_bn254_fr_sparse_matvec_dev: csrc/r1cs.hip)
+_MONT_R = (1 << 256) % _R_ORDER
+
+
+def _limbs_array(vals) -> np.ndarray:
+    """ints (< 2^256) -> (len, 4) u64 little-endian limbs"""
+    buf = b"".join(int(v).to_bytes(32, "little") for v in vals)
+    return np.frombuffer(buf, dtype=np.uint64).reshape(-1, 4).copy()
+
+
+def _compile_host(circuit: CircomCircuit) -> dict:
+    """The host half of compile_circuit (no device).  The rows prepare_prover evaluates -- one per constraint, then one `x_i * 0 = 0`
+    row per input: n = len(constraints) + num_inputs -- padded with empty rows to m = 2^domain_exponent(n), for A, then B, then C: ONE
+    CSR matrix of 3 m rows over the witness (col = variable index, inputs first), the coefficients deduplicated into a table of
+    Montgomery forms.  Returns numpy arrays: row_ptr u32[3 m + 1], col u32[nnz], coeff_id u32[nnz], coeffs (n_coeffs, 4) u64, and the
+    three DensityTrackers (a variable is dense as soon as it OCCURS; A tracks the aux variables only: prover.rs:49-88)."""
+    from .bellman import DensityTracker
+
+    num_inputs, num_aux = circuit.num_inputs, circuit.num_aux
+    n_constraints = len(circuit.constraints)
+    n = n_constraints + num_inputs
+    exp = domain_exponent(n)
+    m = 1 << exp
+    table = {}
+    lens = np.zeros(3 * m, dtype=np.int64)
+    cols, ids, nnz_of = [], [], []
+    for k in range(3):
+        for i, constraint in enumerate(circuit.constraints):
+            lc = constraint[k]
+            lens[k * m + i] = len(lc)
+            for idx, coeff in lc:
+                cols.append(idx)
+                ids.append(table.setdefault(coeff % _R_ORDER, len(table)))
+        if k == 0:                                    # x_i * 0 = 0: the A combination is the input itself
+            one = table.setdefault(1, len(table))
+            lens[n_constraints:n] = 1
+            cols.extend(range(num_inputs))
+            ids.extend([one] * num_inputs)
+        nnz_of.append(len(cols))
+    col = np.asarray(cols, dtype=np.int64)
+    if col.size and (int(col.min()) < 0 or int(col.max()) >= num_inputs + num_aux):
+        raise ValueError("a constraint names a variable the circuit does not have")
+    row_ptr = np.zeros(3 * m + 1, dtype=np.int64)
+    np.cumsum(lens, out=row_ptr[1:])
+    if int(row_ptr[-1]) >= 1 << 32 or len(table) >= 1 << 32:
+        raise ValueError("the circuit has 2^32 terms or more")
+    a_cols, b_cols = col[:nnz_of[0] - num_inputs], col[nnz_of[0]:nnz_of[1]]     # (the input rows of A hold inputs only)
+    a_aux, b_in, b_aux = np.zeros(num_aux, dtype=bool), np.zeros(num_inputs, dtype=bool), np.zeros(num_aux, dtype=bool)
+    a_aux[a_cols[a_cols >= num_inputs] - num_inputs] = True
+    b_in[b_cols[b_cols < num_inputs]] = True
+    b_aux[b_cols[b_cols >= num_inputs] - num_inputs] = True
+    values = sorted(table, key=table.get)
+    coeffs = _limbs_array(v * _MONT_R % _R_ORDER for v in values) if values else np.zeros((0, 4), dtype=np.uint64)
+    return {"num_inputs": num_inputs, "num_aux": num_aux, "n": n, "exp": exp, "m": m,
+            "row_ptr": row_ptr.astype(np.uint32), "col": col.astype(np.uint32), "coeff_id": np.asarray(ids, dtype=np.uint32), "coeffs": coeffs,
+            "a_aux_density": DensityTracker.from_bools(a_aux), "b_input_density": DensityTracker.from_bools(b_in),
+            "b_aux_density": DensityTracker.from_bools(b_aux)}
+
+
+def _all_below_r(w: np.ndarray) -> bool:
+    """every row of the (n, 4) u64 array, read as a little-endian integer, is < r"""
+    mask = (1 << 64) - 1
+    rl = [np.uint64((_R_ORDER >> (64 * i)) & mask) for i in range(4)]
+    if not w.shape[0] or bool((w[:, 3] < rl[3]).all()):   # (the usual case: one pass over the top limbs)
+        return True
+    lt, eq = np.zeros(w.shape[0], dtype=bool), np.ones(w.shape[0], dtype=bool)
+    for i in (3, 2, 1, 0):
+        lt |= eq & (w[:, i] < rl[i])
+        eq &= w[:, i] == rl[i]
+    return bool(lt.all())
+
+
+class CompiledCircuit:
+    """A circuit's witness-independent half on a device (compile_circuit): the CSR matrix of _compile_host as device tensors (u32
+    arrays as int32 views, the coefficient table as (n_coeffs, 4) int64) and the density maps."""
+
+    def __init__(self, host: dict, device):
+        import torch
+
+        self.device = torch.device(device)
+        self.num_inputs, self.num_aux, self.n, self.exp, self.m = (host[k] for k in ("num_inputs", "num_aux", "n", "exp", "m"))
+        self.nnz, self.n_coeffs = int(host["col"].shape[0]), int(host["coeffs"].shape[0])
+        up = lambda a, t: torch.from_numpy(np.ascontiguousarray(a).view(t)).to(self.device)  # noqa: E731
+        self.row_ptr, self.col, self.coeff_id = up(host["row_ptr"], np.int32), up(host["col"], np.int32), up(host["coeff_id"], np.int32)
+        self.coeffs = up(host["coeffs"], np.int64)
+        self.a_aux_density, self.b_input_density, self.b_aux_density = host["a_aux_density"], host["b_input_density"], host["b_aux_density"]
+
+
+def _cptr(t):
+    import ctypes as C
+
+    return C.c_void_p(t.data_ptr()) if t.numel() else None
+
+
+def compile_circuit(circuit: CircomCircuit, device) -> CompiledCircuit:
+    """Everything prepare_prover does that does not depend on the witness, once per circuit: the term lists of the A, B and C
+    combinations as one CSR matrix on `device`, validated there once (mi355zk_bn254_fr_sparse_matvec_check_dev: the evaluating call
+    does not report a bad index), and the three density maps.  The circuit's witness, if it has one, is not read."""
+    import torch
+
+    from . import lib as _lib
+    from .bellman import DeviceError, _stream_ptr
+
+    cc = CompiledCircuit(_compile_host(circuit), device)
+    with torch.cuda.device(cc.device):
+        rc = _lib.load().mi355zk_bn254_fr_sparse_matvec_check_dev(_cptr(cc.row_ptr), _cptr(cc.col), _cptr(cc.coeff_id), cc.n_coeffs,
+                                                                  cc.num_inputs + cc.num_aux, 3 * cc.m, cc.nnz, _stream_ptr())
+    if rc == _lib.ERR_BAD_ARGS:
+        raise ValueError("mi355zk_bn254_fr_sparse_matvec_check_dev: the compiled matrix is not a valid CSR structure")
+    if rc != 0:
+        raise DeviceError(f"mi355zk fr_sparse_matvec_check failed rc={rc}")
+    return cc
+
+
+def prepare_prover_dev(compiled: CompiledCircuit, witness):
+    """prepare_prover on a compiled circuit.  witness: the list of ints witness_from_json returns, or an (n_vars, 4) u64 array of
+    canonical values (a value >= r is a ValueError), inputs first.  One upload, the conversion to Montgomery form, ONE sparse product into a
+    fresh (3 m, 4) tensor whose three m-row slices are a, b and c (their zero padding written by the empty rows: from_coeffs has
+    nothing to append); the assignments are slices of the converted witness.  Same bytes and densities as prepare_prover."""
+    import ctypes as C
+
+    import torch
+
+    from . import lib as _lib
+    from . import prover as _prover
+    from .bellman import DeviceError, _stream_ptr
+
+    n_vars = compiled.num_inputs + compiled.num_aux
+    if isinstance(witness, (list, tuple)):
+        if len(witness) != n_vars:
+            raise ValueError("the witness does not have one value per variable")
+        w = _limbs_array(v % _R_ORDER for v in witness) if n_vars else np.zeros((0, 4), dtype=np.uint64)
+    else:
+        w = np.ascontiguousarray(witness, dtype=np.uint64)
+        if w.shape != (n_vars, 4):
+            raise ValueError("the witness does not have one value of 4 x u64 per variable")
+        if not _all_below_r(w):
+            raise ValueError("the witness holds a value >= r: canonical values required")
+        if not w.flags.writeable:
+            w = w.copy()                                  # (torch.from_numpy wants a writable array; nothing is written)
+    lib = _lib.load()
+    m = compiled.m
+    with torch.cuda.device(compiled.device):
+        d_w = torch.from_numpy(w.view(np.int64)).to(compiled.device)
+        out = torch.empty((3 * m, 4), dtype=torch.int64, device=compiled.device)
+        rc = lib.mi355zk_bn254_fr_from_repr_dev(_cptr(d_w), _cptr(d_w), n_vars, _stream_ptr())
+        if rc == 0:
+            rc = lib.mi355zk_bn254_fr_sparse_matvec_dev(C.c_void_p(out.data_ptr()), _cptr(compiled.row_ptr), _cptr(compiled.col), _cptr(compiled.coeff_id),
+                                                        _cptr(compiled.coeffs), compiled.n_coeffs, _cptr(d_w), n_vars, 3 * m, compiled.nnz, _stream_ptr())
+    if rc != 0:
+        raise DeviceError(f"mi355zk fr_sparse_matvec failed rc={rc}")
+    return _prover.ProvingAssignment(out[:m], out[m:2 * m], out[2 * m:], d_w[:compiled.num_inputs], d_w[compiled.num_inputs:],
+                                     compiled.a_aux_density, compiled.b_input_density, compiled.b_aux_density)
+
+
 def filter_params(params):
     """filter_params (circom_circuit.rs:271-277): vk.ic, h, a, b_g1 and b_g2 without their points at infinity (the A / B queries
     are what the density maps index; l is left as it is, as in the reference)."""
@@ -268,13 +426,21 @@ def filter_params(params):
     return dict(params, vk=vk, h=keep(params["h"]), a=keep(params["a"]), b_g1=keep(params["b_g1"]), b_g2=keep(params["b_g2"]))
 
 
-def prove(pool, circuit: CircomCircuit, params, r: int, s: int):
+def prove(pool, circuit: CircomCircuit, params, r: int, s: int, compiled: CompiledCircuit = None):
     """prove (circom_circuit.rs:187-191) with the blinding scalars given (create_random_proof draws them from the RNG):
-    returns the proof (a, b, c) as raw affine records.  params: the "params" dict of mpc_parameters_new / read_mpc_parameters."""
+    returns the proof (a, b, c) as raw affine records.  params: the "params" dict of mpc_parameters_new / read_mpc_parameters.
+    compiled: compile_circuit(circuit, device) -- the witness is then evaluated on the device (prepare_prover_dev); same proof."""
     from . import prover as _prover
 
     p = filter_params(params)
     host = lambda t: t.cpu().numpy().view(np.uint64).reshape(-1)  # noqa: E731
     vk = {k: host(p["vk"][k]) for k in ("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "delta_g2")}
-    assignment = prepare_prover(circuit, p["h"].device)
+    if compiled is None:
+        assignment = prepare_prover(circuit, p["h"].device)
+    else:
+        if circuit.witness is None:
+            raise SynthesisError("AssignmentMissing")
+        if (compiled.num_inputs, compiled.num_aux, compiled.n) != (circuit.num_inputs, circuit.num_aux, len(circuit.constraints) + circuit.num_inputs):
+            raise ValueError("`compiled` was not compiled from this circuit (variable or constraint counts differ)")
+        assignment = prepare_prover_dev(compiled, circuit.witness)
     return _prover.create_proof(pool, _prover.Parameters(vk, p["h"], p["l"], p["a"], p["b_g1"], p["b_g2"]), assignment, r, s)

@@ -78,6 +78,9 @@ SIGNATURES = {
     "mi355zk_bn254_fr_mul_assign_dev": (_i, [_vp, _vp, _sz, _vp]),
     "mi355zk_bn254_fr_sub_assign_dev": (_i, [_vp, _vp, _sz, _vp]),
     "mi355zk_bn254_fr_into_repr_dev": (_i, [_vp, _vp, _sz, _vp]),
+    "mi355zk_bn254_fr_from_repr_dev": (_i, [_vp, _vp, _sz, _vp]),
+    "mi355zk_bn254_fr_sparse_matvec_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _sz, _sz, _vp]),
+    "mi355zk_bn254_fr_sparse_matvec_check_dev": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp]),
     "mi355zk_bn254_fr_divide_by_z_on_coset_dev": (_i, [_vp, _u32, _vp]),
     "mi355zk_bn254_fr_h_combine_dev": (_i, [_vp, _vp, _vp, _sz, _u32, _vp]),
     "mi355zk_bn254_fr_h_poly_dev": (_i, [_vp, _vp, _vp, _u32, _u32, _vp]),
