@@ -30,6 +30,35 @@
 
 namespace zk {
 
+// Copies of a record made of whole 16-byte words (alignas(16), sizeof a multiple of 16) between memory and registers: one
+// dwordx4 access per word on the device, a plain copy on the host.
+template <class T>
+__host__ __device__ __forceinline__ T copy16_load(const T* p) {
+  static_assert(alignof(T) % 16 == 0 && sizeof(T) % 16 == 0, "16-byte copies");
+#if defined(__HIP_DEVICE_COMPILE__)
+  T r;
+  const uint4* q = reinterpret_cast<const uint4*>(p);
+  uint4* d = reinterpret_cast<uint4*>(&r);
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(T) / 16); ++i) d[i] = q[i];
+  return r;
+#else
+  return *p;
+#endif
+}
+template <class T>
+__host__ __device__ __forceinline__ void copy16_store(T* p, const T& v) {
+  static_assert(alignof(T) % 16 == 0 && sizeof(T) % 16 == 0, "16-byte copies");
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint4* s = reinterpret_cast<const uint4*>(&v);
+  uint4* d = reinterpret_cast<uint4*>(p);
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(T) / 16); ++i) d[i] = s[i];
+#else
+  *p = v;
+#endif
+}
+
 // A multiexp whose exponents arrive in CHUNKS: the host-buffer entry point (host_entry.hip: msm_host_entry) uploads them over PCIe while
 // the kernels of the earlier chunks run.  msm_device (msm_impl.hpp) evaluates chunk c = exponents [cuts[c], cuts[c+1]) when told
 // where they are, with ONE geometry and ONE bucket array for the whole call.

@@ -10,9 +10,7 @@
 #include <cstring>
 
 #include "../../include/mi355zk.h"
-#include "curveu.hpp"
-#include "glv.hpp"
-#include "device_util.hpp"
+#include "window_mul.hpp"
 
 namespace zk {
 namespace {
@@ -476,11 +474,12 @@ int mi355zk_selftest_g2_accumulate(int mode, const uint64_t* affine_pts, const u
   });
 }
 
-// k * P for ONE G2 point on the HOST with the program batch_exp_win_u2_kernel runs (table 1P..8P, signed 4-bit windows, 256
-// doublings) on the U-form Fq2 Jacobian arithmetic of curveu.hpp.  out = memory-format Jacobian X, Y, Z (24 u64).
+// k * P for ONE G2 point on the HOST: window_mul.hpp's program as batch_exp_win_u2_kernel<false> instantiates it (65 plain windows over
+// any 256-bit scalar, order-two canonicalisation), over a stack table of stride 1.  out = memory-format Jacobian X, Y, Z (24 u64).
 int mi355zk_selftest_g2_scalar_mul_u(const uint64_t affine_pt[16], const uint64_t scalar[4], uint64_t out_xyz[24]) {
   return zk::abi_guard([&]() -> int {
     if (!affine_pt || !scalar || !out_xyz) return ZK_ERR_BAD_ARGS;
+    using W = zk::WindowMul<zk::G2U, false, 65>;
     zk::G2Affine base;
     std::memcpy(&base, affine_pt, 128);
     uint32_t s[8];
@@ -488,25 +487,13 @@ int mi355zk_selftest_g2_scalar_mul_u(const uint64_t affine_pt[16], const uint64_
     zk::JacU2 acc = zk::JacU2::zero();
     if (!base.is_zero()) {
       zk::JacTabU2 tab[8];
-      tab[0] = zk::jacu2_tab_from_affine(base.x, base.y);
-      for (int e = 2; e <= 8; ++e) {
-        const zk::JacTabU2& src = tab[(e & 1) ? e - 2 : e / 2 - 1];
-        zk::JacU2 q{src.x, src.y, src.z};
-        if (e & 1) zk::jacu2_add_tab(q, tab[0], false);
-        else q = zk::jacu2_double(q);
-        tab[e - 1] = zk::jacu2_tab_entry(q);
-      }
-      int dig[65];
-      uint32_t carry = 0;
-      for (int j = 0; j < 64; ++j) {
-        uint32_t d = ((s[j >> 3] >> (4 * (j & 7))) & 15u) + carry;
-        carry = d > 8u ? 1u : 0u;
-        dig[j] = carry ? (int)d - 16 : (int)d;
-      }
-      for (int j = 63; j >= 0; --j) {
-        for (int rep = 0; rep < 4; ++rep) acc = zk::jacu2_double(acc);
-        if (dig[j]) zk::jacu2_add_tab(acc, tab[(dig[j] < 0 ? -dig[j] : dig[j]) - 1], dig[j] < 0);
-      }
+      tab[0] = zk::G2U::tab_entry(zk::G2U::from_affine(base));
+      W::Mag mag1, mag2;
+      W::Sgn sgn1, sgn2;
+      bool neg1, neg2;
+      zk::G2U::Endo endo;
+      W::digits(s, mag1, sgn1, mag2, sgn2, neg1, neg2, endo);
+      for (int step = 0; step < W::STEPS; ++step) acc = W::exec<true>(acc, W::decode(step, mag1, sgn1, mag2, sgn2, neg1, neg2), tab, 1, endo);
     }
     const zk::Jacobian<zk::Fq2> r = zk::jacu2_to_std(acc);
     std::memcpy(out_xyz, &r, sizeof r);

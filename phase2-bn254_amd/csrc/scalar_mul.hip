@@ -19,9 +19,7 @@
 #include <vector>
 
 #include "../../include/mi355zk.h"
-#include "curveu.hpp"
-#include "glv.hpp"
-#include "device_util.hpp"
+#include "window_mul.hpp"
 
 #include "api_internal.hpp"
 
@@ -283,24 +281,7 @@ __global__ void __launch_bounds__(256) batch_exp_same_kernel(Affine<Fq>* __restr
 
 // G2: the same fixed signed 4-bit windows on the U-form Fq2 Jacobian accumulator of curveu.hpp (JacU2: 29-bit lazy limbs, one
 // v_mad_u64_u32 per partial product, shared Montgomery reductions) -- round 1 ran this on memory-format Fq2 at 9 Mpoint/s.
-// Table build and main loop run through ONE loop with a single inlined jacu2_double and a single inlined jacu2_add_tab: the Fq2
-// group law is > 100 KB of code per copy.
-//   step = (load entry, double?, add entry, store entry); entries 1..8 hold 1P..8P (with Z^2, Z^3), 0 = none.
-__device__ __forceinline__ JacTabU2 tabu2_load(const JacTabU2* p) {
-  JacTabU2 r;
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  uint4* d = reinterpret_cast<uint4*>(&r);
-#pragma unroll
-  for (int i = 0; i < (int)(sizeof(JacTabU2) / 16); ++i) d[i] = q[i];
-  return r;
-}
-__device__ __forceinline__ void tabu2_store(JacTabU2* p, const JacTabU2& v) {
-  const uint4* s = reinterpret_cast<const uint4*>(&v);
-  uint4* d = reinterpret_cast<uint4*>(p);
-#pragma unroll
-  for (int i = 0; i < (int)(sizeof(JacTabU2) / 16); ++i) d[i] = s[i];
-}
-
+// Table build and main loop are the one-loop program of window_mul.hpp (a single inlined jacu2_double and jacu2_add_tab).
 // SPLIT = true: the scalar goes over the twist's endomorphism psi (glv.hpp: k P = k1 P + k2 psi(P), k1, k2 < 2^128 -- 33 windows of four
 // doublings instead of 64).  psi(P) = mu P holds in the order-r subgroup ONLY, so this form runs only under the caller's promise
 // MI355ZK_G2_TRUSTED_SUBGROUP.  SPLIT = false (the default): 65 plain windows over the whole 256-bit scalar -- the group law and nothing
@@ -328,74 +309,18 @@ __global__ void __launch_bounds__(256) batch_exp_win_u2_kernel(Affine<Fq2>* __re
   const Affine<Fq2> base = bases[same_base ? 0 : (base_index ? base_index[i] : i)];
   JacU2 acc = JacU2::zero();
   if (!base.is_zero()) {
-    tabu2_store(tab + t, jacu2_tab_from_affine(base.x, base.y));
-    // signed digits d_j in [-8, 8]: m = sum d_j 16^j.  SPLIT: of both halves (five words each); plain: of the scalar (eight words and the carry)
-    constexpr int NW = SPLIT ? 5 : 9;
-    uint32_t mag1[NW], mag2[SPLIT ? 5 : 1], sgn1[(NW + 3) / 4], sgn2[2];
-    Fq2U cxU, cyU;
-    if constexpr (SPLIT) {
-      const Glv2Split g = glv2_split(s);
-      signed_nibbles<5, 5>(g.k1, mag1, sgn1);
-      signed_nibbles<5, 5>(g.k2, mag2, sgn2);
-      const FqU C266 = UPow2<FqParams, 266>::get();
-      const Fq2 cxs = glv2_cx(), cys = glv2_cy();
-      cxU = Fq2U{u_mul(u_from_std(cxs.c0), C266), u_mul(u_from_std(cxs.c1), C266)};   // 2^261 domain, < 2p
-      cyU = Fq2U{u_mul(u_from_std(cys.c0), C266), u_mul(u_from_std(cys.c1), C266)};
-    } else {
-      signed_nibbles<9, 8>(s, mag1, sgn1);
-    }
-    // table program, one nibble per field (load, double, add, store):  2P = 2*1P, 3P = 2P + 1P, 4P = 2*2P, 5P = 4P + 1P, ...
-    constexpr uint32_t PROG[7] = {0x1102, 0x0013, 0x2104, 0x0015, 0x3106, 0x0017, 0x4108};
-    // SPLIT: all nibbles of the five limbs (canonical scalars use 33); plain: the 64 nibbles and the carry out of the last (doubling infinity returns at once)
-    constexpr int WINDOWS = SPLIT ? 40 : 65, PER = SPLIT ? 5 : 4;
+    // SPLIT: all nibbles of the five limbs of a half (canonical scalars use 33); plain: the 64 nibbles and the carry out of the last, and the
+    // order-two canonicalisation
+    using W = WindowMul<G2U, SPLIT, SPLIT ? 40 : 65>;
+    copy16_store(tab + t, G2U::tab_entry(G2U::from_affine(base)));
+    typename W::Mag mag1, mag2;
+    typename W::Sgn sgn1, sgn2;
+    bool neg1, neg2;
+    G2U::Endo endo;
+    W::digits(s, mag1, sgn1, mag2, sgn2, neg1, neg2, endo);
 #pragma unroll 1
-    for (int step = 0; step < 7 + PER * WINDOWS; ++step) {
-      uint32_t load = 0, dbl_it = 0, add = 0, store = 0, negate = 0, psi = 0;
-      if (step < 7) {
-        const uint32_t pr = PROG[step];
-        load = pr >> 12;
-        dbl_it = (pr >> 8) & 15u;
-        add = (pr >> 4) & 15u;
-        store = pr & 15u;
-      } else {
-        const int m = step - 7;        // per window: four doublings (the fourth adds the k1 digit), then (SPLIT) the k2 digit through psi
-        if (m == 0) acc = JacU2::zero();
-        const int win = m / PER, sub = m - PER * win, j = WINDOWS - 1 - win;
-        if (sub < 4) {
-          dbl_it = 1;
-          if (sub == 3) {
-            add = (mag1[j >> 3] >> (4 * (j & 7))) & 15u;
-            negate = (sgn1[j >> 5] >> (j & 31)) & 1u;
-          }
-        } else {
-          add = (mag2[j >> 3] >> (4 * (j & 7))) & 15u;
-          negate = (sgn2[j >> 5] >> (j & 31)) & 1u;
-          psi = 1;
-        }
-      }
-      if (load) {
-        const JacTabU2 e = tabu2_load(tab + (uint64_t)(load - 1) * n_chunk + t);
-        acc = JacU2{e.x, e.y, e.z};
-      }
-      if (dbl_it) {
-        acc = jacu2_double(acc);
-        if constexpr (!SPLIT)
-          if (u_is_zero_lt2p(acc.z.c0) && u_is_zero_lt2p(acc.z.c1)) acc = JacU2::zero();   // 2 Y Z == 0: Y == 0, a point of order two
-      }
-      if (add) {
-        JacTabU2 e = tabu2_load(tab + (uint64_t)(add - 1) * n_chunk + t);
-        if constexpr (SPLIT) {
-          if (psi) e = jacu2_tab_psi(e, cxU, cyU);
-          jacu2_add_tab(acc, e, negate != 0);
-        } else {
-          if (!e.z.limbs_all_zero()) {                        // (d P == infinity for a small d: only off the twist)
-            jacu2_add_tab(acc, e, negate != 0);
-            if (u_is_zero_lt2p(acc.z.c0) && u_is_zero_lt2p(acc.z.c1)) acc = JacU2::zero();   // (the addition doubles when acc == e)
-          }
-        }
-      }
-      if (store) tabu2_store(tab + (uint64_t)(store - 1) * n_chunk + t, jacu2_tab_entry(acc));
-    }
+    for (int step = 0; step < W::STEPS; ++step)
+      acc = W::template exec<!SPLIT>(acc, W::decode(step, mag1, sgn1, mag2, sgn2, neg1, neg2), tab + t, n_chunk, endo);
   }
   const Jacobian<Fq2> r = jacu2_to_std(acc);
   out[i] = Affine<Fq2>{r.x, r.y};

@@ -1,5 +1,5 @@
 """The point FFTs on the device against the edge table of tests/point_fft_edge_inputs.py (proven on the CPU by test_point_fft_edges_host.py):
-vectors of multiples of one point, on which the butterflies of pfft_stage_kernel / pfft2_stage_kernel meet equal operands (the doubling branch of
+vectors of multiples of one point, on which the butterflies of pfft_stage_kernel (G1 and G2 instances) meet equal operands (the doubling branch of
 jacu_add_tab / jacu2_add_tab behind a 33- or 64-window multiplication), opposite ones, infinite u or t under unit and non-unit twiddles, and leave
 whole normalisation groups of infinities -- every record of every vector byte for byte against the oracle's Point<G> FFT + batch_normalization, against
 the big-int closed form where the family has one, and fft(ifft(v)) == v == ifft(fft(v)).  G1 at every log_n of 1..9, G2 at 1..7 through the plain windows and

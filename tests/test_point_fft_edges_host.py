@@ -1,7 +1,7 @@
 """The point-FFT edge table (tests/point_fft_edge_inputs.py) proven on the CPU: every vector's closed form against the oracle's
 EvaluationDomain<Point<G>>::{fft, ifft} + batch_normalization, ifft(fft(v)) == v through the oracle, the big-int side of the table against
 the oracle's scalar multiplication, and -- restated as assertions on the scalars -- what each family makes the butterflies of
-pfft_stage_kernel / pfft2_stage_kernel meet.  tests/test_gpu_point_fft_edges.py runs the same table on the device."""
+pfft_stage_kernel (G1 and G2 instances) meets.  tests/test_gpu_point_fft_edges.py runs the same table on the device."""
 import numpy as np
 import pytest
 

@@ -316,9 +316,12 @@ def test_g2_u_accumulation_long_chain(lib):
 
 
 def test_g2_scalar_mul_on_u_form_jacobian_host(lib):
-    """The U-form Fq2 Jacobian arithmetic (jacu2_double, jacu2_add_tab, table entries) run on the HOST through the same
-    windowed program as batch_exp_win_u2_kernel, against the oracle's mul_assign + into_affine: random scalars, 0, 1, 2, r - 1,
-    digits that hit every table entry and both signs."""
+    """The U-form Fq2 Jacobian arithmetic (jacu2_double, jacu2_add_tab, table entries) run on the HOST through the windowed
+    program of window_mul.hpp exactly as batch_exp_win_u2_kernel<false> instantiates it (65 plain windows), against the oracle's
+    mul_assign + into_affine: random scalars, 0, 1, 2, r - 1, digits that hit every table entry and both signs.
+    Then scalars that are ANY 256 bits, as the kernel's are: 2^256 - 1 and 0x8888...8888 over all eight words (the carry out of
+    nibble 63 lands in the 65th window), 2^255 and r itself (k P = infinity).  Their expectations are bn254_model's curve
+    multiplication by the raw integer (no reduction mod r anywhere)."""
     pts = inputs.bases_progression_cpu(2, 6, seed=77)
     ks = [0, 1, 2, 8, 9, 0x8888, 0xFFFFFFFF, M.R_ORDER - 1, M.R_ORDER - 2] + [rnd.randrange(M.R_ORDER) for _ in range(12)]
     for idx, k in enumerate(ks):
@@ -328,3 +331,10 @@ def test_g2_scalar_mul_on_u_form_jacobian_host(lib):
         assert lib.mi355zk_selftest_g2_scalar_mul_u(p.ctypes.data, kl.ctypes.data, out.ctypes.data) == 0
         want = O.G2.to_affine(O.G2.mul(O.G2.from_affine(p), kl))
         assert np.array_equal(O.G2.to_affine(out), want), hex(k)
+    for idx, k in enumerate([(1 << 256) - 1, int("8" * 64, 16), 1 << 255, M.R_ORDER]):
+        p = pts[idx % len(pts)]
+        kl = np.array(M.to_limbs(k), dtype=np.uint64)
+        out = np.zeros(24, np.uint64)
+        assert lib.mi355zk_selftest_g2_scalar_mul_u(p.ctypes.data, kl.ctypes.data, out.ctypes.data) == 0
+        want = M.ec_mul(M.FQ2_OPS, M.g2_affine_from_raw(p), k)
+        assert M.g2_affine_from_raw(O.G2.to_affine(out)) == want, hex(k)
