@@ -339,6 +339,12 @@ int mi355zk_bn254_fr_h_poly_dev(void *d_a, void *d_b, void *d_c, uint32_t log_n,
 int mi355zk_bn254_fr_h_poly(uint64_t *h, const uint64_t *a, const uint64_t *b, const uint64_t *c, size_t len, uint32_t log_n, uint32_t flags);
 /* EvaluationDomain::z (domain.rs:207-212): out = tau^(2^log_n) - 1, Montgomery in and out (host arithmetic). */
 int mi355zk_bn254_fr_domain_z(uint32_t log_n, const uint64_t tau[4], uint64_t out[4]);
+/* out[i] = coeff * base^i for i < n, Montgomery in and out (device array of n x 32 B; base and coeff by value from the host): the powers of
+ * tau of groth16/generator.rs:256-269 (per-chunk `pow` and a running product there) and, with coeff = z(tau) / delta, the H-query exponents
+ * of :288-296.  The host squares base 31 times; every lane owns 16 consecutive indices, forms coeff * base^(16 lane) from the set bits of
+ * its index (at most 28 products) and walks its run with one product per element.  Operand range as for mul_assign above.  Asynchronous
+ * on `stream`.  n == 0 succeeds and launches nothing.  3 = a NULL pointer with n > 0, n >= 2^32. */
+int mi355zk_bn254_fr_powers_dev(void *d_out, const uint64_t base[4], const uint64_t coeff[4], size_t n, void *stream);
 /* Measured Montgomery-product rate of this library (the integer-ALU roofline the kernels are priced
  * against): `blocks` x 256 lanes each run 4 independent chains of `iters` products.  which: 0 Fq, 1 Fr.
  * out[0..3] = a*b^iters (Montgomery arithmetic, lane 0, chain 0) for a parity check; *ms = kernel time. */
@@ -361,6 +367,11 @@ int mi355zk_selftest_glv2_split(const uint32_t k[8], uint32_t out[10]);
 int mi355zk_selftest_g2_psi(const uint64_t affine_pt[16], uint64_t out_xyz[24]);
 int mi355zk_selftest_g2_scalar_mul_u(const uint64_t affine_pt[16], const uint64_t scalar[4], uint64_t out_xyz[24]);
 int mi355zk_selftest_g2_accumulate(int mode, const uint64_t *affine_pts, const uint8_t *negate, size_t n, uint64_t out_xyzz[32]);
+/* the fixed-base program of csrc/fixed_base.hpp on the host: the 32 signed 8-bit digits of k (sum digits[w] 2^(8 w) == k for k < r), and
+ * k * base through the same recoding, step program and addition routine as the kernels, every table entry it needs computed by a plain host
+ * scalar multiplication (group: 1 = G1, 8 + 8 u64; 2 = G2, 16 + 16 u64; 3 = a base the table build would refuse) */
+int mi355zk_selftest_fixed_base_digits(const uint64_t k[4], int16_t digits[32]);
+int mi355zk_selftest_fixed_base_mul(int group, const uint64_t *base_affine, const uint64_t k[4], uint64_t *out_affine);
 
 /* ---- self-test hook ON THE DEVICE: one primitive of csrc/field.hpp / fieldu.hpp / curveu.hpp per lane, on operands the caller chose, so
  * that the gfx950 object code -- and the code that exists in the device pass only: the Montgomery product of mont_mul_gfx950.inc, the quad-
@@ -458,6 +469,27 @@ int mi355zk_bn254_g2_point_fft_dev(void *d_points_affine, uint32_t log_n, int mo
  * SURVEY 8f row 1); used here to synthesise tau-table-like bases on the device. */
 int mi355zk_bn254_g1_batch_mul_dev(void *d_out_affine, const uint64_t base_affine[8], const void *d_scalars, size_t n, void *stream);
 int mi355zk_bn254_g2_batch_mul_dev(void *d_out_affine, const uint64_t base_affine[16], const void *d_scalars, size_t n, void *stream);
+/* ---- fixed-base scalar multiplication over a WINDOW TABLE of one base: out[i] = k[i] * P with no doubling per scalar.  The generator of
+ * groth16/generator.rs:178-510 multiplies ONE generator by a scalar per variable (:406-426) and per H coefficient (:288-296) through
+ * `Wnaf::base(..).scalar(..)` tables; batch_mul_dev above runs a whole variable-base multiplication (~254 doublings + ~66 additions) for
+ * each.  Here the table holds (j * 2^(8 w)) * P for the 32 signed 8-bit windows w and j = 1 .. 128 (4096 affine entries), and a scalar costs
+ * at most 32 mixed additions.  The entry format is the library's own: allocate mi355zk_fixed_base_table_bytes(group) bytes (1 = G1, 2 = G2;
+ * 0 for anything else) and treat them as opaque.
+ * build: one-time work, SYNCHRONISES `stream`; the 4096 entries come from the per-point batch_exp kernels over the scalars j * 2^(8 w) mod r.
+ *   That reduction is sound in the order-r group only, so the base must be a non-infinite point of it -- G1: on the curve; G2: passing the
+ *   membership test of mi355zk_bn254_g2_subgroup_check_dev (run on the host here).  3 (before any device work) = a NULL pointer, table_bytes
+ *   too small, the all-zero record, a record off the curve, a twist point outside the subgroup.
+ * mul: d_scalars = n canonical FrRepr (32 B each), or n Montgomery Fr with MI355ZK_FIXED_SCALARS_MONTGOMERY in `flags` (the kernel applies
+ *   into_repr first, so Fr results feed it without a separate pass); out[i] = the affine record of k[i] * P, all-zero = infinity, which is
+ *   what k = 0 gives.  A scalar >= r gives an UNSPECIFIED record for that element only: nothing faults, nothing outside the table is read,
+ *   the other records are exact.  Asynchronous on `stream`; n == 0 succeeds and launches nothing.  d_table: a table built by the call above
+ *   for the same group (not checked).  3 = a NULL pointer with n > 0, unknown flag bits, n >= 2^31. */
+#define MI355ZK_FIXED_SCALARS_MONTGOMERY 1u
+size_t mi355zk_fixed_base_table_bytes(int group);
+int mi355zk_bn254_g1_fixed_base_build_dev(void *d_table, size_t table_bytes, const uint64_t base_affine[8], void *stream);
+int mi355zk_bn254_g2_fixed_base_build_dev(void *d_table, size_t table_bytes, const uint64_t base_affine[16], void *stream);
+int mi355zk_bn254_g1_fixed_base_mul_dev(void *d_out_affine, const void *d_table, const void *d_scalars, size_t n, uint32_t flags, void *stream);
+int mi355zk_bn254_g2_fixed_base_mul_dev(void *d_out_affine, const void *d_table, const void *d_scalars, size_t n, uint32_t flags, void *stream);
 /* ---- per-point batch exponentiation out[i] = k[i] * P[i] (powersoftau `batch_exp`, batched_accumulator.rs:1130-1181) or, with
  * MI355ZK_EXP_SAME_SCALAR in `mode`, out[i] = k[0] * P[i] (phase2 contribute, phase2/src/parameters.rs:423-470), normalised to affine
  * like `batch_normalization` (ec.rs:251-299); the all-zero record is infinity on both sides.  mode: MI355ZK_EXP_SAME_SCALAR |

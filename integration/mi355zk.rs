@@ -106,6 +106,7 @@ extern "C" {
     pub fn mi355zk_bn254_fr_h_poly_dev(d_a: *mut c_void, d_b: *mut c_void, d_c: *mut c_void, log_n: u32, flags: u32, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_fr_h_poly(h: *mut u64, a: *const u64, b: *const u64, c: *const u64, len: usize, log_n: u32, flags: u32) -> c_int;
     pub fn mi355zk_bn254_fr_domain_z(log_n: u32, tau: *const u64 /* [4] */, out: *mut u64 /* [4] */) -> c_int;
+    pub fn mi355zk_bn254_fr_powers_dev(d_out: *mut c_void, base: *const u64 /* [4] */, coeff: *const u64 /* [4] */, n: usize, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_g1_sparse_matvec_dev(d_out_affine: *mut c_void, d_bases_affine: *const c_void, n_bases: usize, d_row_ptr: *const u32, d_col: *const u32, d_coeffs: *const c_void, n_rows: usize, nnz: usize, stream: *mut c_void, flags: c_int) -> c_int;
     pub fn mi355zk_bn254_g2_sparse_matvec_dev(d_out_affine: *mut c_void, d_bases_affine: *const c_void, n_bases: usize, d_row_ptr: *const u32, d_col: *const u32, d_coeffs: *const c_void, n_rows: usize, nnz: usize, stream: *mut c_void, flags: c_int) -> c_int;
     pub fn mi355zk_bn254_g1_sparse_matvec(out_affine: *mut u8, bases_affine: *const u8, n_bases: usize, row_ptr: *const u32, col: *const u32, coeffs: *const u64, n_rows: usize, nnz: usize, flags: c_int) -> c_int;
@@ -118,6 +119,11 @@ extern "C" {
     pub fn mi355zk_bn254_g2_point_fft_dev(d_points_affine: *mut c_void, log_n: u32, mode: c_int, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_g1_batch_mul_dev(d_out_affine: *mut c_void, base_affine: *const u64 /* [8] */, d_scalars: *const c_void, n: usize, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_g2_batch_mul_dev(d_out_affine: *mut c_void, base_affine: *const u64 /* [16] */, d_scalars: *const c_void, n: usize, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_fixed_base_table_bytes(group: c_int) -> usize;
+    pub fn mi355zk_bn254_g1_fixed_base_build_dev(d_table: *mut c_void, table_bytes: usize, base_affine: *const u64 /* [8] */, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_bn254_g2_fixed_base_build_dev(d_table: *mut c_void, table_bytes: usize, base_affine: *const u64 /* [16] */, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_bn254_g1_fixed_base_mul_dev(d_out_affine: *mut c_void, d_table: *const c_void, d_scalars: *const c_void, n: usize, flags: u32, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_bn254_g2_fixed_base_mul_dev(d_out_affine: *mut c_void, d_table: *const c_void, d_scalars: *const c_void, n: usize, flags: u32, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_g1_batch_exp_dev(d_out_affine: *mut c_void, d_bases_affine: *const c_void, d_scalars: *const c_void, n: usize, mode: c_int, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_g2_batch_exp_dev(d_out_affine: *mut c_void, d_bases_affine: *const c_void, d_scalars: *const c_void, n: usize, mode: c_int, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_g1_batch_exp(out_affine: *mut u8, bases_affine: *const u8, scalars: *const u64, n: usize, mode: c_int) -> c_int;

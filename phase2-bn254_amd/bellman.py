@@ -245,6 +245,49 @@ class MsmTable:
             raise DeviceError(f"mi355zk msm_table_build rc={rc}")
 
 
+class FixedBaseTable:
+    """The window table of ONE base point for fixed-base scalar multiplication (mi355zk_bn254_g{1,2}_fixed_base_build_dev): what
+    `Wnaf::base(g, n)` is to groth16/generator.rs:178-510.  `base` is a raw affine record ((8,) / (16,) u64, host), a non-infinite point of
+    the order-r group; anything else raises ValueError.  mul(scalars) returns the affine records of scalars[i] * base as an (n, 8) / (n, 16)
+    int64 device tensor (all-zero = infinity); it is asynchronous on the current stream."""
+
+    def __init__(self, base, device=None):
+        import torch
+
+        base = np.ascontiguousarray(np.asarray(base, dtype=np.uint64).reshape(-1))
+        assert base.size in (8, 16)
+        lib = _lib.load()
+        self.limbs = int(base.size)
+        self.group = {8: 1, 16: 2}[self.limbs]
+        nbytes = int(lib.mi355zk_fixed_base_table_bytes(self.group))
+        self.device = torch.device("cuda") if device is None else torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.table = torch.empty(nbytes // 8, dtype=torch.int64, device=self.device)   # (the entry format is the library's own)
+        fn = lib.mi355zk_bn254_g1_fixed_base_build_dev if self.group == 1 else lib.mi355zk_bn254_g2_fixed_base_build_dev
+        with torch.cuda.device(self.device):
+            rc = fn(C.c_void_p(self.table.data_ptr()), nbytes, base.ctypes.data_as(C.c_void_p), _stream_ptr())
+        if rc == _lib.ERR_BAD_ARGS:
+            raise ValueError("fixed_base_build: the base is not a non-infinite point of the order-r group")
+        if rc != 0:
+            raise DeviceError(f"mi355zk fixed_base_build rc={rc}")
+
+    def mul(self, scalars, montgomery: bool = False):
+        """scalars: (n, 4) int64 device tensor of canonical FrRepr, or of Montgomery Fr with montgomery=True"""
+        import torch
+
+        assert _is_torch(scalars) and scalars.is_cuda and scalars.is_contiguous() and scalars.dtype == torch.int64 and scalars.device == self.device
+        n = scalars.numel() // 4
+        out = torch.empty((n, self.limbs), dtype=torch.int64, device=self.device)
+        fn = _lib.load().mi355zk_bn254_g1_fixed_base_mul_dev if self.group == 1 else _lib.load().mi355zk_bn254_g2_fixed_base_mul_dev
+        with torch.cuda.device(self.device):
+            rc = fn(C.c_void_p(out.data_ptr()), C.c_void_p(self.table.data_ptr()), C.c_void_p(scalars.data_ptr()), n,
+                    _lib.FIXED_SCALARS_MONTGOMERY if montgomery else 0, _stream_ptr())
+        if rc != 0:
+            raise DeviceError(f"mi355zk fixed_base_mul rc={rc}")
+        return out
+
+
 def multiexp(pool: Worker, bases, density_map, exponents, window_group=None, scalars_montgomery: bool = False) -> _Ready:
     """bellman/src/multiexp.rs:330.  (window_group = (groups, index), device-resident data only: the partial sum over one
     of `groups` equal groups of scalar windows -- multi-GPU sharding by windows, shard.py; None = the whole multiexp.

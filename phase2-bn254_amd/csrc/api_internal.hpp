@@ -2,12 +2,14 @@
 //   api.hip         the C ABI: argument checking, domain constants, device-resident entry points, profiling hooks, lifecycle
 //   host_entry.hip  the host-buffer entry points: Source / Density plan, bases cache, streamed upload, multi-GPU cells
 //   scalar_mul.hip  the scalar-multiplication kernels and their launchers: batch_exp / batch_mul / window-table build / G2 membership
+//   fixed_base.hip  one base, a window table of its multiples, no doublings per scalar (fixed_base.hpp: the program shared with the host)
 //   (msm_g1.hip, msm_g2.hip, ntt.hip, point_fft*.hip, codec.hip, field_ops.hip, records.hip: the kernels behind the functions declared below)
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
+#include <mutex>
 #include <vector>
 
 #include "curveu.hpp"
@@ -65,6 +67,13 @@ extern template int msm_table_build<2>(const void*, size_t, void*, size_t, void*
 int g2_subgroup_flags(const void* d_points, size_t n, void* stream, uint8_t* d_member);
 int g2_subgroup_check(const void* d_points, size_t n, void* stream, long long* bad_index);
 bool g2_in_subgroup_host(const Affine<Fq2>& p);   // the membership test of the kernels, run on the host (self-test hook)
+bool g1_on_curve_host(const Affine<Fq>& p);       // y^2 == x^3 + 3, as the split kernels test it
+// the per-(device, stream) scratch of the scalar-multiplication launchers (Z coordinates between a kernel and its normalisation; grow-only) and
+// the mutex their callers hold while ENQUEUEING: the kernels of one call must reach the stream back to back (see batch_exp)
+int exp_scratch(size_t bytes, void* stream, void** out);
+extern std::mutex g_exp_launch_mu;
+int batch_normalize_g1(void* d_io_affine, const void* d_z, uint64_t n, hipStream_t st);
+int batch_normalize_g2(void* d_io_affine, const void* d_z, uint64_t n, hipStream_t st);
 void exp_scratch_release_all();
 void mul_slots_release_all();
 
@@ -86,6 +95,7 @@ int records_pack_run(int group, const void* d_raw, size_t n, const RecordLayout&
 // field_ops.hip
 int fr_h_combine(Fr* d_a, const Fr* d_b, const Fr* d_c, size_t n, const Fr& zinv, hipStream_t st);   // a[i] = (a[i] * b[i] - c[i]) * zinv, one pass
 int fr_into_repr(Fr* d_out, const Fr* d_in, size_t n, hipStream_t st);                                // Montgomery -> canonical (d_out may alias d_in)
+int fr_powers(Fr* d_out, const Fr& base, const Fr& coeff, size_t n, hipStream_t st);               // out[i] = coeff * base^i (Montgomery)
 
 // api.hip
 int domain_op_dev(Fr* d_a, uint32_t log_n, int op, hipStream_t st);   // EvaluationDomain::{fft, ifft, coset_fft, icoset_fft} on a device array

@@ -53,6 +53,29 @@ __global__ void __launch_bounds__(256) fr_into_repr_kernel(Fr* out, const Fr* in
     st(out + i, to_canonical(ld(in + i)));
 }
 
+// out[i] = coeff * base^i: every lane owns FR_POW_RUN consecutive indices.  It forms coeff * base^(16 lane) from the set bits of its index over
+// the host's squarings sq[j] = base^(2^j) (at most 28 products: n < 2^32), then walks its run with one product per element.  Montgomery
+// products throughout, so every element is the canonical residue whatever the order of the factors.
+constexpr int FR_POW_RUN = 16;
+struct FrSquarings {
+  Fr sq[32];
+};
+__global__ void __launch_bounds__(256) fr_powers_kernel(Fr* __restrict__ out, const FrSquarings t, Fr coeff, uint64_t n) {
+  const uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t i0 = lane * FR_POW_RUN;
+  if (i0 >= n) return;
+  Fr cur = coeff;
+#pragma unroll 1
+  for (int b = 0; b < 28; ++b)
+    if ((lane >> b) & 1u) cur = mul(cur, t.sq[b + 4]);
+  const Fr base = t.sq[0];
+#pragma unroll 1
+  for (int k = 0; k < FR_POW_RUN && i0 + k < n; ++k) {
+    st(out + i0 + k, cur);
+    cur = mul(cur, base);
+  }
+}
+
 // every lane runs `iters` dependent products x <- x * y on 4 independent chains (ILP like the group law)
 template <class PR>
 __global__ void __launch_bounds__(256) fp_mul_ubench_kernel(Fp<PR> a, Fp<PR> b, uint32_t iters, Fp<PR>* out) {
@@ -123,6 +146,16 @@ int fr_into_repr(Fr* d_out, const Fr* d_in, size_t n, hipStream_t st) {
   uint64_t blocks = (n + 255) / 256;
   if (blocks > 16384) blocks = 16384;
   hipLaunchKernelGGL(fr_into_repr_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_out, d_in, (uint64_t)n);
+  ZK_HIP(hipGetLastError());
+  return ZK_OK;
+}
+int fr_powers(Fr* d_out, const Fr& base, const Fr& coeff, size_t n, hipStream_t st) {
+  if (n == 0) return ZK_OK;
+  FrSquarings t;
+  t.sq[0] = base;
+  for (int j = 1; j < 32; ++j) t.sq[j] = sqr(t.sq[j - 1]);
+  const uint64_t lanes = (n + FR_POW_RUN - 1) / FR_POW_RUN;
+  hipLaunchKernelGGL(fr_powers_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, d_out, t, coeff, (uint64_t)n);
   ZK_HIP(hipGetLastError());
   return ZK_OK;
 }
@@ -507,6 +540,17 @@ int mi355zk_bn254_fr_into_repr_dev(void* d_out, const void* d_in, size_t n, void
   return zk::abi_guard([&]() -> int {
     if ((!d_out || !d_in) && n) return ZK_ERR_BAD_ARGS;
     return zk::fr_into_repr((zk::Fr*)d_out, (const zk::Fr*)d_in, n, (hipStream_t)stream);
+  });
+}
+
+int mi355zk_bn254_fr_powers_dev(void* d_out, const uint64_t base[4], const uint64_t coeff[4], size_t n, void* stream) {
+  return zk::abi_guard([&]() -> int {
+    if ((uint64_t)n >= (1ull << 32) || (n && (!d_out || !base || !coeff))) return ZK_ERR_BAD_ARGS;
+    if (n == 0) return ZK_OK;
+    zk::Fr b, c;
+    std::memcpy(&b, base, 32);
+    std::memcpy(&c, coeff, 32);
+    return zk::fr_powers((zk::Fr*)d_out, b, c, n, (hipStream_t)stream);
   });
 }
 

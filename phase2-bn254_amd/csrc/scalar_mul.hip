@@ -391,7 +391,7 @@ struct ExpScratch {
 static std::mutex g_exp_mu;
 static std::map<std::pair<int, void*>, ExpScratch> g_exp_scratch;
 
-static int exp_scratch(size_t bytes, void* stream, void** out) {
+int exp_scratch(size_t bytes, void* stream, void** out) {
   int dev = 0;
   ZK_HIP(hipGetDevice(&dev));
   std::lock_guard<std::mutex> lk(g_exp_mu);
@@ -486,7 +486,7 @@ __global__ void __launch_bounds__(256) exp_classify_kernel(Affine<F>* __restrict
 // The scratch (Z coordinates, window tables) is per (device, stream) and the two kernels of one call must reach the stream
 // back to back: several host threads may share a stream (the default one above all), and A.exp, B.exp, A.normalize would
 // let A normalise with B's Z.  Held while ENQUEUEING only; the stream orders the kernels.
-static std::mutex g_exp_launch_mu;
+std::mutex g_exp_launch_mu;
 
 template <class F>
 int batch_exp(void* d_out, const void* d_bases, int same_base, const void* d_scalars, int same_scalar, size_t n, void* stream,
@@ -801,6 +801,7 @@ int msm_table_build(const void* d_bases, size_t n, void* d_table, size_t table_b
 }
 
 bool g2_in_subgroup_host(const Affine<Fq2>& p) { return g2_in_subgroup(p); }
+bool g1_on_curve_host(const Affine<Fq>& p) { return g1_on_curve(p); }
 
 template int batch_exp<Fq>(void*, const void*, int, const void*, int, size_t, void*, const uint32_t*, bool, bool, const uint8_t*);
 template int batch_exp<Fq2>(void*, const void*, int, const void*, int, size_t, void*, const uint32_t*, bool, bool, const uint8_t*);

@@ -18,6 +18,7 @@ MSM_SCALARS_MONTGOMERY = 1
 NO_FLAG, PIN_TABLES = (1 << 64) - 1, 1   # MI355ZK_NO_FLAG (inf_off: no infinity flag byte) / MI355ZK_PIN_TABLES (include/mi355zk.h)
 ABI_VERSION = 7   # MI355ZK_ABI_VERSION of the include/mi355zk.h this table was written against: load() refuses another library
 H_INTO_REPR = 1   # MI355ZK_H_INTO_REPR: flags of fr_h_poly[_dev]
+FIXED_SCALARS_MONTGOMERY = 1   # MI355ZK_FIXED_SCALARS_MONTGOMERY: flags of fixed_base_mul_dev
 EXP_SAME_SCALAR, FFT_INVERSE, G2_TRUSTED_SUBGROUP = 1, 1, 2   # mode / flag bits of batch_exp, point_fft, sparse_matvec (include/mi355zk.h)
 
 _vp, _sz, _i, _u32 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32
@@ -86,6 +87,7 @@ SIGNATURES = {
     "mi355zk_bn254_fr_h_poly_dev": (_i, [_vp, _vp, _vp, _u32, _u32, _vp]),
     "mi355zk_bn254_fr_h_poly": (_i, [_vp, _vp, _vp, _vp, _sz, _u32, _u32]),
     "mi355zk_bn254_fr_domain_z": (_i, [_u32, _vp, _vp]),
+    "mi355zk_bn254_fr_powers_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "mi355zk_ubench_fp_mul": (_i, [_i, _u32, _u32, _vp, _vp, _vp, C.POINTER(C.c_float)]),
     "mi355zk_selftest_g1_record_sum": (_i, [_i, _vp, _vp, _vp, _sz, _sz, _vp]),
     "mi355zk_selftest_g2_record_sum": (_i, [_i, _vp, _vp, _vp, _sz, _sz, _vp]),
@@ -115,6 +117,13 @@ SIGNATURES = {
     "mi355zk_bn254_g2_point_fft_dev": (_i, [_vp, _u32, _i, _vp]),
     "mi355zk_bn254_g1_batch_mul_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "mi355zk_bn254_g2_batch_mul_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "mi355zk_fixed_base_table_bytes": (_sz, [_i]),
+    "mi355zk_bn254_g1_fixed_base_build_dev": (_i, [_vp, _sz, _vp, _vp]),
+    "mi355zk_bn254_g2_fixed_base_build_dev": (_i, [_vp, _sz, _vp, _vp]),
+    "mi355zk_bn254_g1_fixed_base_mul_dev": (_i, [_vp, _vp, _vp, _sz, _u32, _vp]),
+    "mi355zk_bn254_g2_fixed_base_mul_dev": (_i, [_vp, _vp, _vp, _sz, _u32, _vp]),
+    "mi355zk_selftest_fixed_base_digits": (_i, [_vp, _vp]),
+    "mi355zk_selftest_fixed_base_mul": (_i, [_i, _vp, _vp, _vp]),
     "mi355zk_bn254_g1_batch_exp": (_i, [_vp, _vp, _vp, _sz, _i]),
     "mi355zk_bn254_g2_batch_exp": (_i, [_vp, _vp, _vp, _sz, _i]),
     "mi355zk_bn254_g1_batch_exp_dev": (_i, [_vp, _vp, _vp, _sz, _i, _vp]),
