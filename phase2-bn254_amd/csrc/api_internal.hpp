@@ -23,7 +23,7 @@ int ntt_run_batch(Fr* const* d_arrays, uint32_t batch, uint32_t log_n, const Fr&
 int ntt_scale(Fr* d_a, uint32_t log_n, const Fr& c, const Fr* g, hipStream_t st);
 void ntt_release_all();
 int ntt_configure();
-// msm_g1.hip, msm_g2.hip (the kernels and msm_device: msm_impl.hpp)
+// msm_g1.hip, msm_g2.hip (the kernels: msm_impl.hpp; msm_device: msm_host.hpp)
 int msm_g1_device(const void* d_bases, uint64_t n_bases, uint64_t base_offset, const void* d_scalars, uint64_t n, const uint32_t* d_density,
                   const uint32_t* d_dprefix, hipStream_t st, uint64_t out_xyz[12], long long* err_index, uint32_t wgroups, uint32_t wgroup, bool scalars_mont,
                   MsmChunks* chunks, uint64_t table_stride = 0, uint32_t table_c = 0);

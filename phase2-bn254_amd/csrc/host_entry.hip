@@ -145,7 +145,7 @@ template <int GROUP>
 int msm_dev_entry(const void* d_bases, size_t n_bases, size_t base_offset, const void* d_scalars, size_t n_scalars,
                   const uint32_t* density, size_t density_bits, void* stream, uint64_t* out_xyz, uint32_t wgroups, uint32_t wgroup,
                   uint32_t flags, MsmChunks* chunks, bool table) {
-  // table: d_bases is the window table msm_table_build made of a vector of n_bases points (table mode, msm_impl.hpp)
+  // table: d_bases is the window table msm_table_build made of a vector of n_bases points (table mode, msm_host.hpp)
   // chunks != nullptr: the exponents are handed over chunk by chunk while the call runs (msm_host_entry); d_scalars is unused
   t_last_err_index = -1;
   if (!out_xyz || (n_scalars && !d_scalars && !chunks) || (n_bases && !d_bases)) return ZK_ERR_BAD_ARGS;
@@ -216,7 +216,7 @@ struct BasesEntry {
   uint64_t tick = 0;
   bool ready = false;      // fully uploaded
   std::mutex fill_mu;      // held by the call that uploads it
-  // the vector's WINDOW TABLE (table mode, msm_impl.hpp), for vectors pinned with mi355zk_bases_cache_pin_tables: built by the first
+  // the vector's WINDOW TABLE (table mode, msm_host.hpp), for vectors pinned with mi355zk_bases_cache_pin_tables: built by the first
   // call that finds the entry ready, counted against the cache's capacity, freed with the entry
   bool want_table = false, table_failed = false;
   void* table = nullptr;

@@ -1,6 +1,6 @@
-// G1 instantiation of the Pippenger pipeline (msm_impl.hpp); see there for the design.
+// G1 instantiation of the Pippenger pipeline (kernels: msm_impl.hpp, see there for the design; host driver: msm_host.hpp).
 #define ZK_CHAIN_MAD 1  // fieldu.hpp u_mad: one dependent mad chain per column (measured faster in this TU)
-#include "msm_impl.hpp"
+#include "msm_host.hpp"
 
 namespace zk {
 
@@ -17,7 +17,7 @@ int msm_g1_device(const void* d_bases, uint64_t n_bases, uint64_t base_offset, c
 }
 
 void msm_geometry(uint64_t n, uint32_t wgroups, uint32_t* c, uint32_t* W) {
-  MsmGeom G = choose_geom(n, 1, wgroups ? wgroups : 1);
+  MsmGeom G = choose_geom(n, 1, wgroups ? wgroups : 1, msm_knobs());
   *c = G.c;
   *W = G.W;
 }
@@ -25,7 +25,7 @@ void msm_geometry(uint64_t n, uint32_t wgroups, uint32_t* c, uint32_t* W) {
 // table mode (msm_device): the window layout a table of n_bases points is built for -- width[w] bits per window, window w scaled by
 // 2^(width[0] + .. + width[w-1])
 void msm_table_geometry(uint64_t n_bases, int group, uint32_t* c, uint32_t* W, uint8_t width[64]) {
-  const MsmGeom G = make_geom(table_window_bits(n_bases, group));
+  const MsmGeom G = make_geom(table_window_bits(n_bases, group, msm_knobs()));
   *c = G.c;
   *W = G.W;
   if (width) for (uint32_t w = 0; w < 64; ++w) width[w] = w < G.W ? G.width[w] : 0;
@@ -57,7 +57,7 @@ int segsum_g1_device(const void* d_points, uint64_t nnz, const uint32_t* d_row_p
 // (0 = no bucket) for the windows produced, INT32_MIN elsewhere; geom = {c, W, nb, rmul, rshift, width[0..W), shift[0..W)}.
 int msm_selftest_digits(uint64_t n, uint32_t wgroups, const uint32_t scalar[8], uint32_t w_start, uint32_t w_stop, int direct, int32_t* digits,
                         uint32_t* geom) {
-  const MsmGeom G = choose_geom(n, 1, wgroups ? wgroups : 1);
+  const MsmGeom G = choose_geom(n, 1, wgroups ? wgroups : 1, msm_knobs());
   if (G.W == 0) return ZK_ERR_BAD_ARGS;
   if (geom) {
     geom[0] = G.c; geom[1] = G.W; geom[2] = G.nb; geom[3] = G.rmul; geom[4] = G.rshift;

@@ -1,5 +1,5 @@
-// G2 instantiation of the Pippenger pipeline (msm_impl.hpp); see there for the design.
-#include "msm_impl.hpp"
+// G2 instantiation of the Pippenger pipeline (kernels: msm_impl.hpp, see there for the design; host driver: msm_host.hpp).
+#include "msm_host.hpp"
 
 namespace zk {
 

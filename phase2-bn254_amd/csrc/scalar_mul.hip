@@ -733,7 +733,7 @@ int batch_mul(void* d_out, const uint64_t* base_raw, const void* d_scalars, size
   return ZK_OK;
 }
 
-// Window table of a base vector for table-mode multiexps (msm_impl.hpp: msm_device with table_stride != 0):
+// Window table of a base vector for table-mode multiexps (msm_host.hpp: msm_device with table_stride != 0):
 //   table[w * n + i] = 2^(width[0] + .. + width[w-1]) * bases[i],  w < W,  affine records (the identity stays the identity).
 // Window w + 1 is window w doubled width[w] times: PLAIN doublings on the U-form Jacobian accumulator (X, Y parked in the output
 // plane, Z in scratch), then one batched normalisation (one inversion per 16 / 8 points).  Exact for EVERY point the decoders admit:
