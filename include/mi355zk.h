@@ -514,6 +514,52 @@ int mi355zk_bn254_g2_batch_exp(uint8_t *out_affine, const uint8_t *bases_affine,
 int mi355zk_bn254_g2_subgroup_check_dev(const void *d_points_affine, size_t n, void *stream, long long *bad_index);
 int mi355zk_selftest_g2_in_subgroup(const uint64_t affine_pt[16]);   /* host run of the same test: 1 / 0 */
 
+/* ---- the pairing e: G1 x G2 -> GT (Engine::miller_loop + final_exponentiation, pairing/src/bn256/mod.rs:57-226) in its batched form: many
+ * independent pairing PRODUCTS in one call -- every same_ratio of a verify_transformation (powersoftau/src/utils.rs:151-159), the four
+ * pairings per contribution of MPCParameters::verify (phase2/src/parameters.rs:529-659), the three-pair product of each of many proofs
+ * (bellman/src/groth16/verifier.rs:36-67).  One lane runs one Miller loop; a segmented product joins the values of a group; one lane per
+ * group runs the final exponentiation.
+ * Points: raw affine records, 64 B (G1) / 128 B (G2), the all-zero record = infinity; a pair with one contributes the value one (mod.rs:68).
+ * DOMAIN: G1 points on the curve, G2 points on the twist AND in the order-r subgroup.  Like the reference, the library tests neither;
+ * outside the domain the values are unspecified and nothing faults.  mi355zk_bn254_g2_subgroup_check_dev establishes it for untrusted G2 data.
+ * A GT value is 384 B: twelve Fq as Montgomery u64[4] limbs in the order c0.c0.c0, c0.c0.c1, c0.c1.c0, ..., c1.c2.c1 (Fq12 -> Fq6 -> Fq2 ->
+ * Fq, the reference's struct order).  After the final exponentiation it is a unique, fully reduced field element: equal values are equal
+ * bytes, here and in the reference. */
+/* out[g] = final_exponentiation( prod_{i in [group_ptr[g], group_ptr[g+1])} miller(P_i, Q_i) ), 384 B each; an empty group gives one.
+   d_group_ptr: n_groups + 1 uint32 on the device, nondecreasing from 0 to n_pairs.  It is NOT checked (it is the caller's device data):
+   entries are clamped to n_pairs, so a bad array gives unspecified values and no access out of range.
+   d_group_ptr == NULL: every pair is its own group (n_groups must equal n_pairs).  Asynchronous on `stream`; n_groups == 0 succeeds and
+   launches nothing.  The Miller values live in one stream-ordered allocation of 384 B per pair, released on `stream` by the call itself.
+   3 = NULL pointer with n > 0, n_pairs or n_groups >= 2^31, d_group_ptr == NULL with n_groups != n_pairs. */
+int mi355zk_bn254_pairing_product_dev(void *d_gt_out, const void *d_g1_affine, const void *d_g2_affine, size_t n_pairs,
+                                      const uint32_t *d_group_ptr, size_t n_groups, void *stream);
+/* flags[g] = 1 iff gt[g] is one / iff gt_a[g] == gt_b[g] (bytes); for callers that want booleans only.  Asynchronous on `stream`. */
+int mi355zk_bn254_gt_is_one_dev(uint8_t *d_flags, const void *d_gt, size_t n, void *stream);
+int mi355zk_bn254_gt_eq_dev(uint8_t *d_flags, const void *d_gt_a, const void *d_gt_b, size_t n, void *stream);
+/* the same product for ONE group on the host, single thread, no device needed (the same arithmetic compiled for the host): the
+   once-per-key pairing of prepare_verifying_key (verifier.rs:19-34).  n_pairs == 0 gives one.  3 = NULL pointer, n_pairs >= 2^31. */
+int mi355zk_bn254_pairing_product(uint64_t gt_out[48], const uint64_t *g1_affine, const uint64_t *g2_affine, size_t n_pairs);
+/* one tower primitive on the host.  Operands and result are Fq12 (48 words), Fq6 (24) or Fq2 (8) in the formats above, concatenated in
+   `in` in the order given; in_words / out_words must be exactly the op's (3 otherwise, as for an unknown op or a NULL pointer):
+     FQ6_MUL a b -> a b          FQ6_INV a -> 1 / a (0 for 0)       FQ6_MUL_BY_01 a b0 b1 -> a (b0 + b1 v)      FQ6_MUL_BY_1 a b1 -> a b1 v
+     FQ12_MUL a b -> a b         FQ12_SQR a -> a^2                  FQ12_INV a -> 1 / a (0 for 0)               FQ12_CONJUGATE a -> a^(q^6)
+     FQ12_FROBENIUS_k a -> a^(q^k), k = 1, 2, 3                     FQ12_MUL_BY_034 a c0 c3 c4 -> a (c0 + (c3 + c4 v) w)
+     FINAL_EXPONENTIATION a -> a^((q^12 - 1) / r) */
+#define MI355ZK_PAIRING_OP_FQ6_MUL 0
+#define MI355ZK_PAIRING_OP_FQ6_INV 1
+#define MI355ZK_PAIRING_OP_FQ6_MUL_BY_01 2
+#define MI355ZK_PAIRING_OP_FQ6_MUL_BY_1 3
+#define MI355ZK_PAIRING_OP_FQ12_MUL 4
+#define MI355ZK_PAIRING_OP_FQ12_SQR 5
+#define MI355ZK_PAIRING_OP_FQ12_INV 6
+#define MI355ZK_PAIRING_OP_FQ12_CONJUGATE 7
+#define MI355ZK_PAIRING_OP_FQ12_FROBENIUS_1 8
+#define MI355ZK_PAIRING_OP_FQ12_FROBENIUS_2 9
+#define MI355ZK_PAIRING_OP_FQ12_FROBENIUS_3 10
+#define MI355ZK_PAIRING_OP_FQ12_MUL_BY_034 11
+#define MI355ZK_PAIRING_OP_FINAL_EXPONENTIATION 12
+int mi355zk_selftest_pairing_op(int op, const uint64_t *in, size_t in_words, uint64_t *out, size_t out_words);
+
 /* ---- host-side group helpers on Jacobian results: acc += other (CurveProjective::add_assign,
  * ec.rs:360-454) -- how per-GPU partial sums are joined after the all-gather -- and into_affine
  * (ec.rs:596-629; infinity -> all-zero record). */

@@ -129,6 +129,10 @@ extern "C" {
     pub fn mi355zk_bn254_g1_batch_exp(out_affine: *mut u8, bases_affine: *const u8, scalars: *const u64, n: usize, mode: c_int) -> c_int;
     pub fn mi355zk_bn254_g2_batch_exp(out_affine: *mut u8, bases_affine: *const u8, scalars: *const u64, n: usize, mode: c_int) -> c_int;
     pub fn mi355zk_bn254_g2_subgroup_check_dev(d_points_affine: *const c_void, n: usize, stream: *mut c_void, bad_index: *mut c_longlong) -> c_int;
+    pub fn mi355zk_bn254_pairing_product_dev(d_gt_out: *mut c_void, d_g1_affine: *const c_void, d_g2_affine: *const c_void, n_pairs: usize, d_group_ptr: *const u32, n_groups: usize, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_bn254_gt_is_one_dev(d_flags: *mut u8, d_gt: *const c_void, n: usize, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_bn254_gt_eq_dev(d_flags: *mut u8, d_gt_a: *const c_void, d_gt_b: *const c_void, n: usize, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_bn254_pairing_product(gt_out: *mut u64 /* [48] */, g1_affine: *const u64, g2_affine: *const u64, n_pairs: usize) -> c_int;
     pub fn mi355zk_bn254_g1_add(acc_xyz: *mut u64 /* [12] */, other_xyz: *const u64 /* [12] */) -> c_int;
     pub fn mi355zk_bn254_g2_add(acc_xyz: *mut u64 /* [24] */, other_xyz: *const u64 /* [24] */) -> c_int;
     pub fn mi355zk_bn254_g1_to_affine(out_xy: *mut u64 /* [8] */, xyz: *const u64 /* [12] */) -> c_int;

@@ -5,6 +5,7 @@ Layout:
   lib.py          ctypes loader (fails loudly when the library is missing)
   shard.py        multi-GPU point-range sharding + the all-gather/join exchange step
   generator.py    groth16 generate_parameters (generator.rs:178-510) over fixed-base window tables on the device
+  pairing.py      the checking half: pairing products on the device, same_ratio[_batch], prepare_verifying_key, verify_proof[s]
   prover.py       the caller of the path: groth16 create_proof (prover.rs:202-343) over the device library
   ceremony.py     the ceremony-side callers (batch_exp, merge_pairs, QAP evaluation, point FFT, codecs, file containers)
   bellman.py      host-side mirror of the reference's interface for this path:
@@ -13,7 +14,7 @@ Layout:
 The directory name carries a hyphen (it is the reference's name); import it through the
 repo-root shim module `phase2_bn254_amd`.
 """
-from . import bellman, ceremony, circom, generator, lib, prover, shard  # noqa: F401
+from . import bellman, ceremony, circom, generator, lib, pairing, prover, shard  # noqa: F401
 from .bellman import (  # noqa: F401
     DensityTracker,
     EvaluationDomain,
