@@ -197,6 +197,26 @@ int mi355zk_bn254_g1_dense_multiexp(const uint8_t *bases, const uint64_t *scalar
 int mi355zk_bn254_g2_dense_multiexp(const uint8_t *bases, const uint64_t *scalars, size_t n, uint64_t out_xyz[24]);
 int mi355zk_bn254_g1_merge_pairs(const uint8_t *v1, const uint8_t *v2, const uint64_t *rho, size_t n, uint64_t out_s[12], uint64_t out_sx[12]);
 int mi355zk_bn254_g2_merge_pairs(const uint8_t *v1, const uint8_t *v2, const uint64_t *rho, size_t n, uint64_t out_s[24], uint64_t out_sx[24]);
+/* ---- the random exponents rho of merge_pairs, generated on the device.  The reference draws them from thread_rng (powersoftau/src/utils.rs:
+ * 116-123, phase2/src/utils.rs:79-86); here they are a counter-based stream that a host can reproduce: ChaCha20 (constants "expand 32-byte k",
+ * 20 rounds) with `key` in state words 4..11, a 64-bit block counter in words 12, 13 and `stream_id` in words 14, 15.  Scalar number g (a
+ * 64-bit index) is words 8 (g & 1) .. 8 (g & 1) + 7 of block g >> 1: limb j = word[2 j] | word[2 j + 1] << 32, the top limb masked to 61
+ * bits.  The value is uniform in [0, 2^253) and canonical without rejection (2^253 < r); a random linear combination over such scalars
+ * accepts a false statement with probability 2^-253 per check.  The stream depends on (key, stream_id, g) alone -- not on the launch, not on
+ * how a range is cut into calls or pieces.
+ * fr_random_dev: scalars first .. first + n - 1 as canonical FrRepr (32 B each) at d_out (16-byte aligned); asynchronous on `stream`; n == 0
+ * launches nothing; rc 3 on a NULL pointer, a misaligned d_out or n >= 2^31.  selftest_fr_random: the same values from the same code run on
+ * the host (no device; out may be NULL when n == 0). */
+int mi355zk_bn254_fr_random_dev(void *d_out, size_t n, const uint32_t key[8], uint64_t stream_id, uint64_t first, void *stream);
+int mi355zk_selftest_fr_random(uint64_t *out, size_t n, const uint32_t key[8], uint64_t stream_id, uint64_t first);
+/* merge_pairs with rho = scalars 0 .. n - 1 of the stream (key, stream_id): the _dev forms fill a stream-ordered workspace and run the
+ * multiexp of merge_pairs_dev over it; the host-buffer forms upload no exponents -- every piece fills its own range of the stream on its
+ * device -- so the two sums are the same points for every piece size and every device count.  A verifier takes `key` from the operating
+ * system's generator and a distinct stream_id per vector. */
+int mi355zk_bn254_g1_merge_pairs_random_dev(const void *d_v1, const void *d_v2, size_t n, const uint32_t key[8], uint64_t stream_id, void *stream, uint64_t out_s[12], uint64_t out_sx[12]);
+int mi355zk_bn254_g2_merge_pairs_random_dev(const void *d_v1, const void *d_v2, size_t n, const uint32_t key[8], uint64_t stream_id, void *stream, uint64_t out_s[24], uint64_t out_sx[24]);
+int mi355zk_bn254_g1_merge_pairs_random(const uint8_t *v1, const uint8_t *v2, size_t n, const uint32_t key[8], uint64_t stream_id, uint64_t out_s[12], uint64_t out_sx[12]);
+int mi355zk_bn254_g2_merge_pairs_random(const uint8_t *v1, const uint8_t *v2, size_t n, const uint32_t key[8], uint64_t stream_id, uint64_t out_s[24], uint64_t out_sx[24]);
 /* ONE WINDOW GROUP of a multiexp, for multi-GPU runs that shard by scalar windows as well as by point range: the windows of
  * the geometry chosen for n_scalars (a window count divisible by window_groups) are dealt out in window_groups equal groups
  * and only group `window_group` is evaluated: out = sum over its windows w of B^w * T_w.  The partials of all groups add up

@@ -72,6 +72,11 @@ extern "C" {
     pub fn mi355zk_bn254_g2_dense_multiexp(bases: *const u8, scalars: *const u64, n: usize, out_xyz: *mut u64 /* [24] */) -> c_int;
     pub fn mi355zk_bn254_g1_merge_pairs(v1: *const u8, v2: *const u8, rho: *const u64, n: usize, out_s: *mut u64 /* [12] */, out_sx: *mut u64 /* [12] */) -> c_int;
     pub fn mi355zk_bn254_g2_merge_pairs(v1: *const u8, v2: *const u8, rho: *const u64, n: usize, out_s: *mut u64 /* [24] */, out_sx: *mut u64 /* [24] */) -> c_int;
+    pub fn mi355zk_bn254_fr_random_dev(d_out: *mut c_void, n: usize, key: *const u32 /* [8] */, stream_id: u64, first: u64, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_bn254_g1_merge_pairs_random_dev(d_v1: *const c_void, d_v2: *const c_void, n: usize, key: *const u32 /* [8] */, stream_id: u64, stream: *mut c_void, out_s: *mut u64 /* [12] */, out_sx: *mut u64 /* [12] */) -> c_int;
+    pub fn mi355zk_bn254_g2_merge_pairs_random_dev(d_v1: *const c_void, d_v2: *const c_void, n: usize, key: *const u32 /* [8] */, stream_id: u64, stream: *mut c_void, out_s: *mut u64 /* [24] */, out_sx: *mut u64 /* [24] */) -> c_int;
+    pub fn mi355zk_bn254_g1_merge_pairs_random(v1: *const u8, v2: *const u8, n: usize, key: *const u32 /* [8] */, stream_id: u64, out_s: *mut u64 /* [12] */, out_sx: *mut u64 /* [12] */) -> c_int;
+    pub fn mi355zk_bn254_g2_merge_pairs_random(v1: *const u8, v2: *const u8, n: usize, key: *const u32 /* [8] */, stream_id: u64, out_s: *mut u64 /* [24] */, out_sx: *mut u64 /* [24] */) -> c_int;
     pub fn mi355zk_bn254_g1_msm_part_dev(d_bases: *const c_void, n_bases: usize, base_offset: usize, d_scalars: *const c_void, n_scalars: usize, density: *const u32, density_bits: usize, window_groups: u32, window_group: u32, stream: *mut c_void, out_xyz: *mut u64 /* [12] */) -> c_int;
     pub fn mi355zk_bn254_g2_msm_part_dev(d_bases: *const c_void, n_bases: usize, base_offset: usize, d_scalars: *const c_void, n_scalars: usize, density: *const u32, density_bits: usize, window_groups: u32, window_group: u32, stream: *mut c_void, out_xyz: *mut u64 /* [24] */) -> c_int;
     pub fn mi355zk_bn254_g1_msm_ex_dev(d_bases: *const c_void, n_bases: usize, base_offset: usize, d_scalars: *const c_void, n_scalars: usize, density: *const u32, density_bits: usize, flags: u32, window_groups: u32, window_group: u32, stream: *mut c_void, out_xyz: *mut u64 /* [12] */) -> c_int;

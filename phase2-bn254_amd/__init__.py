@@ -6,6 +6,9 @@ Layout:
   shard.py        multi-GPU point-range sharding + the all-gather/join exchange step
   generator.py    groth16 generate_parameters (generator.rs:178-510) over fixed-base window tables on the device
   pairing.py      the checking half: pairing products on the device, same_ratio[_batch], prepare_verifying_key, verify_proof[s]
+  keys.py         hash_to_g2, the key pairs and public-key records of both ceremonies (host work on single points)
+  verify.py       the ceremony steps and their checks: contribute_mpc_parameters, verify_contribution, verify_mpc_parameters,
+                  contribute_response, verify_transform, next_challenge -- one pairing launch per verification
   prover.py       the caller of the path: groth16 create_proof (prover.rs:202-343) over the device library
   ceremony.py     the ceremony-side callers (batch_exp, merge_pairs, QAP evaluation, point FFT, codecs, file containers)
   bellman.py      host-side mirror of the reference's interface for this path:
@@ -14,7 +17,7 @@ Layout:
 The directory name carries a hyphen (it is the reference's name); import it through the
 repo-root shim module `phase2_bn254_amd`.
 """
-from . import bellman, ceremony, circom, generator, lib, pairing, prover, shard  # noqa: F401
+from . import bellman, ceremony, circom, generator, keys, lib, pairing, prover, shard, verify  # noqa: F401
 from .bellman import (  # noqa: F401
     DensityTracker,
     EvaluationDomain,
@@ -28,4 +31,13 @@ from .bellman import (  # noqa: F401
     multiexp,
     pin_bases,
     unpin_bases,
+)
+from .verify import (  # noqa: F401
+    VerificationError,
+    contribute_mpc_parameters,
+    contribute_response,
+    next_challenge,
+    verify_contribution,
+    verify_mpc_parameters,
+    verify_transform,
 )

@@ -6,6 +6,7 @@ reference functions they replace:
   batch_exp(bases, coeff, same_scalar)     phase2/src/parameters.rs:423-470 (every point by delta^-1)
   dense_multiexp(bases, exponents)         powersoftau/src/utils.rs:189-292
   merge_pairs(v1, v2, rho)                 powersoftau/src/utils.rs:112-131, phase2/src/utils.rs:59-105 (rho drawn by the caller)
+  merge_pairs_random(v1, v2, key, id)      the same with rho generated on the device (fr_random: the ChaCha20 scalar stream of include/mi355zk.h)
   power_pairs(v, rho)                      powersoftau/src/utils.rs:133-135
   eval_qap(bases, row_ptr, col, coeff)     the per-variable sums of MPCParameters::new, phase2/src/parameters.rs:225-294
   point_fft / point_ifft(points)           EvaluationDomain<Point<G>>::{fft, ifft}, powersoftau/src/bin/prepare_phase2.rs:68-131
@@ -121,6 +122,66 @@ def merge_pairs_host(v1: np.ndarray, v2: np.ndarray, rho: np.ndarray):
     fn = _lib.load().mi355zk_bn254_g1_merge_pairs if g == 1 else _lib.load().mi355zk_bn254_g2_merge_pairs
     _check(fn(v1.ctypes.data_as(C.c_void_p), v2.ctypes.data_as(C.c_void_p), rho.ctypes.data_as(C.c_void_p), v1.shape[0], s.ctypes.data_as(C.c_void_p),
               sx.ctypes.data_as(C.c_void_p)), "merge_pairs (host buffers)")
+    return s, sx
+
+
+def _chacha_key(key):
+    """32 bytes (the ChaCha key as little-endian words) or eight u32 -> the C array the entry points take"""
+    if isinstance(key, (bytes, bytearray)):
+        if len(key) != 32:
+            raise ValueError("a ChaCha key has 32 bytes")
+        key = [int.from_bytes(key[4 * i:4 * i + 4], "little") for i in range(8)]
+    key = [int(k) for k in key]
+    if len(key) != 8 or any(k < 0 or k >> 32 for k in key):
+        raise ValueError("a ChaCha key is eight u32 words")
+    return (C.c_uint32 * 8)(*key)
+
+
+def fr_random(n: int, key, stream_id: int = 0, first: int = 0, device=None):
+    """Scalars first .. first + n - 1 of the stream (key, stream_id) as an (n, 4) int64 device tensor of canonical FrRepr, uniform in
+    [0, 2^253): mi355zk_bn254_fr_random_dev, asynchronous on the current stream.  key: 32 bytes or eight u32 words."""
+    import torch
+
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    out = torch.empty((n, 4), dtype=torch.int64, device=device)
+    if n:
+        with torch.cuda.device(device):
+            _check(_lib.load().mi355zk_bn254_fr_random_dev(_p(out), n, _chacha_key(key), stream_id, first, _stream_ptr()), "fr_random")
+    return out
+
+
+def fr_random_host(n: int, key, stream_id: int = 0, first: int = 0) -> np.ndarray:
+    """the same scalars from the library's host run of the generator (mi355zk_selftest_fr_random; no device): (n, 4) u64"""
+    out = np.zeros((n, 4), dtype=np.uint64)
+    _check(_lib.load().mi355zk_selftest_fr_random(out.ctypes.data_as(C.c_void_p), n, _chacha_key(key), stream_id, first), "fr_random (host)")
+    return out
+
+
+def merge_pairs_random(v1, v2, key, stream_id: int = 0):
+    """merge_pairs with rho = scalars 0 .. n - 1 of the stream (key, stream_id), generated on the device into a workspace of the call
+    (mi355zk_bn254_g{1,2}_merge_pairs_random_dev): what a verifier calls -- key from os.urandom, a distinct stream_id per vector."""
+    g = _group(v1)
+    if v1.shape != v2.shape or not (v1.is_contiguous() and v2.is_contiguous()):
+        raise ValueError("merge_pairs_random: two contiguous vectors of one length")
+    s, sx = _to_host_point(g), _to_host_point(g)
+    _check(_fn("merge_pairs_random_dev", g)(_p(v1), _p(v2), v1.shape[0], _chacha_key(key), stream_id, _stream_ptr(), s.ctypes.data_as(C.c_void_p),
+                                            sx.ctypes.data_as(C.c_void_p)), "merge_pairs_random")
+    return s, sx
+
+
+def power_pairs_random(v, key, stream_id: int = 0):
+    """merge_pairs_random(v[:-1], v[1:]) (utils.rs:133-135)"""
+    return merge_pairs_random(v[:-1], v[1:], key, stream_id)
+
+
+def merge_pairs_random_host(v1: np.ndarray, v2: np.ndarray, key, stream_id: int = 0):
+    """merge_pairs_random on HOST arrays (mi355zk_bn254_g{1,2}_merge_pairs_random): the pieces of merge_pairs_host, no exponents uploaded --
+    every piece fills its own range of the stream on its device, so the sums do not depend on the piece size or the device count."""
+    g = {8: 1, 16: 2}[v1.shape[1]]
+    assert v1.flags["C_CONTIGUOUS"] and v2.flags["C_CONTIGUOUS"] and v1.dtype == np.uint64 and v2.dtype == np.uint64 and v1.shape == v2.shape
+    s, sx = _to_host_point(g), _to_host_point(g)
+    _check(_fn("merge_pairs_random", g)(v1.ctypes.data_as(C.c_void_p), v2.ctypes.data_as(C.c_void_p), v1.shape[0], _chacha_key(key), stream_id,
+                                        s.ctypes.data_as(C.c_void_p), sx.ctypes.data_as(C.c_void_p)), "merge_pairs_random (host buffers)")
     return s, sx
 
 
@@ -582,7 +643,7 @@ def write_mpc_parameters(mpc):
 def contribute_parameters(params, delta: int):
     """The device work of MPCParameters::contribute (phase2/src/parameters.rs:414-522) for a given private delta: every point of
     l and h times delta^-1 (`batch_exp`, affine out), delta_g1 and delta_g2 times delta.  Returns new parameters; the key pair,
-    its transcript hash and the public key record (keypair.rs: hash-to-G2, BLAKE2b) stay with the caller."""
+    its transcript hash and the public key record are keys.mpc_keypair's, and verify.contribute_mpc_parameters is the whole step."""
     dev = params["h"].device
     import torch
 

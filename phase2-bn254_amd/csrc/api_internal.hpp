@@ -2,6 +2,7 @@
 //   api.hip         the C ABI: argument checking, domain constants, device-resident entry points, profiling hooks, lifecycle
 //   host_entry.hip  the host-buffer entry points: Source / Density plan, bases cache, streamed upload, multi-GPU cells
 //   scalar_mul.hip  the scalar-multiplication kernels and their launchers: batch_exp / batch_mul / window-table build / G2 membership
+//   fr_random.hip   the random exponents of merge_pairs generated on the device (chacha.hpp: the generator shared with the host)
 //   fixed_base.hip  one base, a window table of its multiples, no doublings per scalar (fixed_base.hpp: the program shared with the host)
 //   (msm_g1.hip, msm_g2.hip, ntt.hip, point_fft*.hip, codec.hip, field_ops.hip, records.hip: the kernels behind the functions declared below)
 #pragma once
@@ -97,6 +98,13 @@ int fr_h_combine(Fr* d_a, const Fr* d_b, const Fr* d_c, size_t n, const Fr& zinv
 int fr_into_repr(Fr* d_out, const Fr* d_in, size_t n, hipStream_t st);                                // Montgomery -> canonical (d_out may alias d_in)
 int fr_powers(Fr* d_out, const Fr& base, const Fr& coeff, size_t n, hipStream_t st);               // out[i] = coeff * base^i (Montgomery)
 
+// fr_random.hip: scalars first .. first + n - 1 of the stream (key, stream_id) of chacha.hpp as canonical FrRepr at d_out (16-byte aligned), enqueued on `st`
+struct FrRandomStream {
+  uint32_t key[8];
+  uint64_t stream_id;
+};
+int fr_random_fill(void* d_out, size_t n, const uint32_t key[8], uint64_t stream_id, uint64_t first, hipStream_t st);
+
 // api.hip
 int domain_op_dev(Fr* d_a, uint32_t log_n, int op, hipStream_t st);   // EvaluationDomain::{fft, ifft, coset_fft, icoset_fft} on a device array
 int domain_op_batch_dev(Fr* const* d_arrays, uint32_t batch, uint32_t log_n, int op, hipStream_t st);
@@ -121,8 +129,9 @@ int msm_host_entry(const uint8_t* bases, size_t n_bases, size_t base_offset, con
                    size_t density_bits, uint64_t* out_xyz, const RecordLayout& L = RecordLayout());
 template <class F>
 int batch_exp_host(uint8_t* out, const uint8_t* bases, const uint64_t* scalars, size_t n, int same_scalar, bool g2_trusted);
+// rnd != nullptr: rho is not read -- every piece fills its exponents on its device from the scalar stream of chacha.hpp, from the piece's first index
 template <int GROUP>
-int dense_host(const uint8_t* v1, const uint8_t* v2, const uint64_t* rho, size_t n, uint64_t* out_s, uint64_t* out_sx);
+int dense_host(const uint8_t* v1, const uint8_t* v2, const uint64_t* rho, size_t n, uint64_t* out_s, uint64_t* out_sx, const FrRandomStream* rnd = nullptr);
 int ntt_host(uint64_t* a, uint32_t log_n, int op, const uint64_t* omega);
 int h_poly_host(uint64_t* h, const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t len, uint32_t log_n, uint32_t flags);
 template <class F>
@@ -137,8 +146,8 @@ extern template int msm_host_entry<1>(const uint8_t*, size_t, size_t, const uint
 extern template int msm_host_entry<2>(const uint8_t*, size_t, size_t, const uint64_t*, size_t, const uint32_t*, size_t, uint64_t*, const RecordLayout&);
 extern template int batch_exp_host<Fq>(uint8_t*, const uint8_t*, const uint64_t*, size_t, int, bool);
 extern template int batch_exp_host<Fq2>(uint8_t*, const uint8_t*, const uint64_t*, size_t, int, bool);
-extern template int dense_host<1>(const uint8_t*, const uint8_t*, const uint64_t*, size_t, uint64_t*, uint64_t*);
-extern template int dense_host<2>(const uint8_t*, const uint8_t*, const uint64_t*, size_t, uint64_t*, uint64_t*);
+extern template int dense_host<1>(const uint8_t*, const uint8_t*, const uint64_t*, size_t, uint64_t*, uint64_t*, const FrRandomStream*);
+extern template int dense_host<2>(const uint8_t*, const uint8_t*, const uint64_t*, size_t, uint64_t*, uint64_t*, const FrRandomStream*);
 extern template int sparse_matvec<Fq>(void*, const void*, size_t, const uint32_t*, const uint32_t*, const void*, size_t, size_t, void*, int, bool, void*, size_t);
 extern template int sparse_matvec<Fq2>(void*, const void*, size_t, const uint32_t*, const uint32_t*, const void*, size_t, size_t, void*, int, bool, void*, size_t);
 extern template int sparse_matvec_host<Fq>(uint8_t*, const uint8_t*, size_t, const uint32_t*, const uint32_t*, const uint64_t*, size_t, size_t, int, bool);

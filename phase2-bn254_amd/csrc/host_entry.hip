@@ -1061,10 +1061,10 @@ int batch_exp_host(uint8_t* out, const uint8_t* bases, const uint64_t* scalars, 
 // device of mi355zk_init's set (one piece uploads -- pageable copies block their thread -- while the other computes); v2 == nullptr:
 // dense_multiexp.  No Source errors (infinity bases add nothing: the reference's dense contract).
 template <int GROUP>
-int dense_host(const uint8_t* v1, const uint8_t* v2, const uint64_t* rho, size_t n, uint64_t* out_s, uint64_t* out_sx) {
+int dense_host(const uint8_t* v1, const uint8_t* v2, const uint64_t* rho, size_t n, uint64_t* out_s, uint64_t* out_sx, const FrRandomStream* rnd) {
   using J = typename std::conditional<GROUP == 1, G1Jacobian, G2Jacobian>::type;
   constexpr size_t rec = GROUP == 1 ? 64 : 128;
-  if (!out_s || (v2 && !out_sx) || (n && (!v1 || !rho)) || n >= (1ull << 31)) return ZK_ERR_BAD_ARGS;
+  if (!out_s || (v2 && !out_sx) || (n && (!v1 || (!rho && !rnd))) || n >= (1ull << 31)) return ZK_ERR_BAD_ARGS;
   J total = J::zero(), total2 = J::zero();
   if (n > 0) {
     std::vector<int> devs;
@@ -1109,11 +1109,14 @@ int dense_host(const uint8_t* v1, const uint8_t* v2, const uint64_t* rho, size_t
         const size_t p0 = i * piece, m = n - p0 < piece ? n - p0 : piece;
         hipError_t e = hipMemcpyAsync(d_v1, v1 + p0 * rec, (m + (shared ? shift : 0)) * rec, hipMemcpyHostToDevice, S->compute);
         if (e == hipSuccess && v2 && !shared) e = hipMemcpyAsync(d_v2, v2 + p0 * rec, m * rec, hipMemcpyHostToDevice, S->compute);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_rho, rho + p0 * 4, m * 32, hipMemcpyHostToDevice, S->compute);
+        if (e == hipSuccess && !rnd) e = hipMemcpyAsync(d_rho, rho + p0 * 4, m * 32, hipMemcpyHostToDevice, S->compute);
         if (e != hipSuccess) {
           std::fprintf(stderr, "[mi355zk] dense multiexp (host buffers): HIP error %d (%s)\n", (int)e, hipGetErrorString(e));
           return ZK_ERR_DEVICE;
         }
+        // (no upload of exponents: scalars p0 .. p0 + m - 1 of the caller's stream, whatever the piece size and whichever device runs the piece)
+        if (rnd)
+          if (int rc = fr_random_fill(d_rho, m, rnd->key, rnd->stream_id, p0, S->compute)) return rc;
         J a = J::zero(), b = J::zero();
         const int rc = GROUP == 1 ? msm_g1_dense_device(d_v1, d_v2, d_rho, m, S->compute, reinterpret_cast<uint64_t*>(&a), v2 ? reinterpret_cast<uint64_t*>(&b) : nullptr)
                                   : msm_g2_dense_device(d_v1, d_v2, d_rho, m, S->compute, reinterpret_cast<uint64_t*>(&a), v2 ? reinterpret_cast<uint64_t*>(&b) : nullptr);
@@ -1371,8 +1374,8 @@ template int msm_host_entry<1>(const uint8_t*, size_t, size_t, const uint64_t*, 
 template int msm_host_entry<2>(const uint8_t*, size_t, size_t, const uint64_t*, size_t, const uint32_t*, size_t, uint64_t*, const RecordLayout&);
 template int batch_exp_host<Fq>(uint8_t*, const uint8_t*, const uint64_t*, size_t, int, bool);
 template int batch_exp_host<Fq2>(uint8_t*, const uint8_t*, const uint64_t*, size_t, int, bool);
-template int dense_host<1>(const uint8_t*, const uint8_t*, const uint64_t*, size_t, uint64_t*, uint64_t*);
-template int dense_host<2>(const uint8_t*, const uint8_t*, const uint64_t*, size_t, uint64_t*, uint64_t*);
+template int dense_host<1>(const uint8_t*, const uint8_t*, const uint64_t*, size_t, uint64_t*, uint64_t*, const FrRandomStream*);
+template int dense_host<2>(const uint8_t*, const uint8_t*, const uint64_t*, size_t, uint64_t*, uint64_t*, const FrRandomStream*);
 template int sparse_matvec<Fq>(void*, const void*, size_t, const uint32_t*, const uint32_t*, const void*, size_t, size_t, void*, int, bool, void*, size_t);
 template int sparse_matvec<Fq2>(void*, const void*, size_t, const uint32_t*, const uint32_t*, const void*, size_t, size_t, void*, int, bool, void*, size_t);
 template int sparse_matvec_host<Fq>(uint8_t*, const uint8_t*, size_t, const uint32_t*, const uint32_t*, const uint64_t*, size_t, size_t, int, bool);

@@ -58,6 +58,12 @@ SIGNATURES = {
     "mi355zk_bn254_g2_dense_multiexp": (_i, [_vp, _vp, _sz, _vp]),
     "mi355zk_bn254_g1_merge_pairs": (_i, [_vp, _vp, _vp, _sz, _vp, _vp]),
     "mi355zk_bn254_g2_merge_pairs": (_i, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    "mi355zk_bn254_fr_random_dev": (_i, [_vp, _sz, _u32p, C.c_uint64, C.c_uint64, _vp]),
+    "mi355zk_selftest_fr_random": (_i, [_vp, _sz, _u32p, C.c_uint64, C.c_uint64]),
+    "mi355zk_bn254_g1_merge_pairs_random_dev": (_i, [_vp, _vp, _sz, _u32p, C.c_uint64, _vp, _vp, _vp]),
+    "mi355zk_bn254_g2_merge_pairs_random_dev": (_i, [_vp, _vp, _sz, _u32p, C.c_uint64, _vp, _vp, _vp]),
+    "mi355zk_bn254_g1_merge_pairs_random": (_i, [_vp, _vp, _sz, _u32p, C.c_uint64, _vp, _vp]),
+    "mi355zk_bn254_g2_merge_pairs_random": (_i, [_vp, _vp, _sz, _u32p, C.c_uint64, _vp, _vp]),
     "mi355zk_bn254_g1_dense_multiexp_dev": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "mi355zk_bn254_g2_dense_multiexp_dev": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "mi355zk_bn254_g1_merge_pairs_dev": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
