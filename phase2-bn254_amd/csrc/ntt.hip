@@ -37,46 +37,11 @@
 
 #include "fieldu.hpp"
 #include "device_util.hpp"
+#include "ntt_plan.hpp"  // NttPassParams, NttBatch, the NTT_* constants; NttKnobs and the planner
 
 namespace zk {
 
 namespace {
-
-constexpr int NTT_MAX_LOG_NP = 12;   // longest sub-transform a tile row can be (kernel instantiations, root tables)
-constexpr int NTT_LOG_NP = 10;       // the pass planner's default: 1024-point rows (longer ones for 2^21 .. 2^23; env MI355ZK_NTT_LOGNP = 10 / 11 / 12 forces)
-constexpr int NTT_TILE_ELEMS = 4096; // G * N_p
-constexpr int NTT_THREADS = 1024;
-
-struct NttPassParams {
-  uint32_t log_np;       // log2(N_p)
-  uint32_t g;            // rows (batch) per tile
-  uint64_t in_xs, in_gs; // element strides (in elements) of transform index / batch index on load
-  uint64_t out_xs, out_gs;
-  // tile -> base offsets: tile id = hi * tiles_lo + lo
-  uint64_t tiles_lo;
-  uint64_t in_hi_stride, in_lo_stride;
-  uint64_t out_hi_stride, out_lo_stride;
-  uint32_t load_x_fastest;  // lane order on load: 1 = transform index fastest (last pass)
-  // inter-pass twiddle  w^(tw_mul * k * (lo*g + gidx)) ; tw_mul == 0 -> none (last pass)
-  uint64_t tw_mul;
-  uint32_t tw_h;            // two-level split: w^e = A[e >> h] * B[e & (2^h - 1)]
-  uint32_t tw_full;         // 1: the first pass of a two-pass transform reads its twiddle w^(k * col) from a table indexed by the OUTPUT position
-  uint32_t pre;             // first pass of coset_fft: element i *= g^i   (1: preA/preB, split pre_h; round 5, folded tables: 2: row position x *= preA[x];
-                            // 3: butterfly twiddles from the stage table preA (wave-local kernel); 4: that, and *= preB[col])
-  uint32_t pre_h;
-  uint32_t post;            // last pass: 1 = multiply by post_c; 2 = by post_c * ginv^k (postA/postB, split post_h); 3 = by nothing; 4 = row output k *= postA[k]; 5 = that, and *= postB[first output index of the row]
-  uint32_t post_h;
-  uint32_t xcd_pair;        // 1: tiles 2j and 2j + 1 run on the same XCD, one dispatch round apart (see the kernel)
-  // (round 5) batch > 1: ONE launch runs this pass of `batch` independent transforms of the same size and kind: workgroup ids
-  // [t * tiles, (t + 1) * tiles) belong to transform t, whose arrays are NttBatch::in[t] / out[t]
-  uint32_t batch;
-  uint64_t tiles;
-};
-constexpr uint32_t NTT_MAX_BATCH = 8;
-struct NttBatch {
-  const Fr* in[NTT_MAX_BATCH];
-  Fr* out[NTT_MAX_BATCH];
-};
 
 // table entry (round 4): a twiddle as the PLAIN canonical integer w on nine 29-bit limbs followed by wq = floor(w * 2^261 / p) --
 // the constant and its quotient of fieldu.hpp's u_mul_shoup -- 72 B, 8-byte aligned (padding the entry to 80 B for aligned 16-byte
@@ -645,270 +610,59 @@ __global__ void ntt_scale_kernel(Fr* a, uint64_t n, Fr c, const UTab* __restrict
   gstore(a + i, u_to_std_lt2p(v));
 }
 
-struct Key {
-  int dev;
-  uint32_t log_n;
-  uint32_t w[8];
-  bool operator<(const Key& o) const {
-    if (dev != o.dev) return dev < o.dev;
-    if (log_n != o.log_n) return log_n < o.log_n;
-    for (int i = 0; i < 8; ++i)
-      if (w[i] != o.w[i]) return w[i] < o.w[i];
-    return false;
-  }
+}  // namespace
+
+}  // namespace zk
+
+#include "ntt_tables.hpp"  // the table cache and the scratch pool: Key, PowTables, tables_make_room, build_pow_tables, build_folded, scratch_for, to_tw
+
+namespace zk {
+
+namespace {
+
+// ONE table of the pass kernels, by (kind, LOG_NP): rows of 2^1 .. 2^12 for the two barrier kernels, 2^8 .. 2^12 for the wave-local one.
+// One instantiation per row length: static stage loops.  ntt_configure walks it, the launcher indexes it.
+using NttPassKernel = void (*)(const Fr*, Fr*, NttPassParams, const UTab*, const UTab*, const UTab*, const UTab*, const UTab*, const UTab*, const UTab*, TwU,
+                               const UTab*, NttBatch);
+constexpr NttPassKernel g_ntt_kernels[NTT_KERNEL_KINDS][NTT_MAX_LOG_NP + 1] = {
+    // [kind][LOG_NP]; no kernel for LOG_NP == 0, nor for wave-local rows shorter than 2^8
+    {nullptr, ntt_pass_kernel<1, false>, ntt_pass_kernel<2, false>, ntt_pass_kernel<3, false>, ntt_pass_kernel<4, false>, ntt_pass_kernel<5, false>,
+     ntt_pass_kernel<6, false>, ntt_pass_kernel<7, false>, ntt_pass_kernel<8, false>, ntt_pass_kernel<9, false>, ntt_pass_kernel<10, false>,
+     ntt_pass_kernel<11, false>, ntt_pass_kernel<12, false>},
+    {nullptr, ntt_pass_kernel<1, true>, ntt_pass_kernel<2, true>, ntt_pass_kernel<3, true>, ntt_pass_kernel<4, true>, ntt_pass_kernel<5, true>,
+     ntt_pass_kernel<6, true>, ntt_pass_kernel<7, true>, ntt_pass_kernel<8, true>, ntt_pass_kernel<9, true>, ntt_pass_kernel<10, true>,
+     ntt_pass_kernel<11, true>, ntt_pass_kernel<12, true>},
+    {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ntt_pass_wl_kernel<8>, ntt_pass_wl_kernel<9>, ntt_pass_wl_kernel<10>,
+     ntt_pass_wl_kernel<11>, ntt_pass_wl_kernel<12>},
 };
-
-// Per (device, log_n, omega) tables; built once and kept (the prover reuses one domain size for
-// every fft of a proof: bellman/src/groth16/prover.rs:217-241).
-// hipMalloc that adds to the owner's byte count (the table cache is bounded by BYTES per device: tables_make_room)
-template <class T>
-static hipError_t tab_malloc(T** p, size_t bytes, size_t* account) {
-  hipError_t e = hipMalloc(p, bytes);
-  if (e == hipSuccess) *account += bytes;
-  return e;
-}
-struct PowTables {
-  size_t bytes = 0;        // device bytes of A, B, roots, full (folded tables count in their own `bytes`)
-  uint32_t h = 0;          // w^e = A[e >> h] * B[e & (2^h-1)], e < 2^log_n
-  UTab* A = nullptr;
-  UTab* B = nullptr;
-  UTab* roots[NTT_MAX_LOG_NP + 1] = {};  // roots[b][x] = (w^(N/2^b))^x, x < 2^(b-1)
-  UTab* full = nullptr;    // two-pass transforms up to NTT_FULL_TW_MAX_LOG: w^(k * col) at the first pass's output position (72 B per element)
-  uint32_t full_log_s = 0;
-  // (round 5) `full` with a transform's scale factors folded in (ntt_full_folded_kernel), one per (pre_g, post_c, post_g) this root has
-  // been used with -- a domain uses two roots with two each: (fft, coset_fft) and (ifft, icoset_fft)
-  struct Folded {
-    size_t bytes = 0;
-    bool has_pre = false, has_post_c = false, has_post_g = false;
-    Fr pre{}, post_c{}, post_g{};
-    uint32_t log_s = 0;
-    UTab* full = nullptr;
-    UTab* pre_rows = nullptr;   // (pre^S)^x, x < N_1
-    UTab* pre_stages = nullptr; // the first pass's butterfly twiddles times the row twist (ntt_stage_table_kernel), N_1 entries
-    UTab* post_rows = nullptr;  // (post^N_1)^k2, k2 < S  (in general: (post^(N / N_last))^k, k < N_last)
-    // transforms without a full table (2^21 and up):
-    bool big = false;
-    UTab* pre_cols = nullptr;    // pre^col, col < N / N_first
-    UTab* post_rowc = nullptr;   // post_c * post^rb, rb < N / N_last: the factor shared by the outputs of one row of the last pass
-    UTab* tw_b_scaled = nullptr; // ifft: the low table B of the two-level twiddle times post_c -- the pass before the last multiplies it in
-    void free_tabs() {
-      (void)hipFree(full); (void)hipFree(pre_rows); (void)hipFree(pre_stages); (void)hipFree(post_rows);
-      (void)hipFree(pre_cols); (void)hipFree(post_rowc); (void)hipFree(tw_b_scaled);
-    }
-  };
-  std::vector<Folded> folded;
-  void free_all() {
-    (void)hipFree(A);
-    (void)hipFree(B);
-    (void)hipFree(full);
-    for (auto* r : roots) (void)hipFree(r);
-    for (auto& f : folded) f.free_tabs();
-    folded.clear();
-  }
-};
-constexpr size_t NTT_FOLDED_MAX = 4;   // per root: a caller cycling through coset generators must not grow device memory without limit
-// Measured (round 3): 2^20 fft 0.1507 -> 0.1456 ms with the table (one product less per element of the first pass, 50 MB more to
-// stream); at 2^22 the 192 MiB table makes the transform SLOWER (0.564 -> 0.580 ms): the pass is VALU-bound only while its streams stay
-// inside the L2 / Infinity Cache.  Hence two-pass transforms up to 2^20 only.
-constexpr uint32_t NTT_FULL_TW_MAX_LOG = 20;
-
-std::mutex g_mu;
-std::map<Key, PowTables> g_tables;
-
-// The cache is keyed on arbitrary roots (best_fft takes a caller-supplied omega): bounded per device, so that a caller cycling through
-// roots cannot grow device memory without limit.  Called ONCE at the start of a transform (under g_run_mu), before any of its up to
-// three table lookups: a drop between two lookups of one call would free the tables the first lookup has just returned (found by the
-// NTT fuzz: 64 + entries in one process).  Dropping this device's entries is safe once the device is idle.
-constexpr size_t NTT_TABLES_MAX = 64;
-// ... and by BYTES: an entry is small up to 2^20 except for its full tables -- 72 B x 2^log_n each, up to 1 + NTT_FOLDED_MAX per
-// root -- so 64 entries could hold ~18 GiB.  Default budget 4 GiB per device (env MI355ZK_NTT_TABLES_GB): a prover's two roots with their
-// folded tables at 2^20 are 0.3 GiB.
-static size_t tables_byte_budget() {
-  static const size_t v = [] {
-    const char* e = std::getenv("MI355ZK_NTT_TABLES_GB");
-    const double gb = e ? std::atof(e) : 4.0;
-    return (size_t)((gb > 0.03125 ? gb : 0.03125) * 1073741824.0);
-  }();
-  return v;
-}
-int tables_make_room(size_t need) {
-  int dev = 0;
-  ZK_HIP(hipGetDevice(&dev));
-  {
-    std::lock_guard<std::mutex> lk(g_mu);
-    size_t mine = 0, bytes = 0;
-    for (auto& kv : g_tables) {
-      if (kv.first.dev != dev) continue;
-      ++mine;
-      bytes += kv.second.bytes;
-      for (auto& f : kv.second.folded) bytes += f.bytes;
-    }
-    if (mine + need <= NTT_TABLES_MAX && bytes <= tables_byte_budget()) return ZK_OK;
-  }
-  // the device drains OUTSIDE g_mu (callers on other devices keep looking their tables up); g_run_mu, held by the caller, keeps new
-  // launches of THIS cache's tables from starting meanwhile
-  ZK_HIP(hipDeviceSynchronize());
-  std::lock_guard<std::mutex> lk(g_mu);
-  for (auto it = g_tables.begin(); it != g_tables.end();) {
-    if (it->first.dev != dev) { ++it; continue; }
-    it->second.free_all();
-    it = g_tables.erase(it);
-  }
-  return ZK_OK;
-}
-
-int build_pow_tables(hipStream_t st, uint32_t log_n, const Fr& w, bool want_roots, const uint32_t* bs, int nb, PowTables** out,
-                     uint32_t full_log_s = 0) {
-  int dev = 0;
-  ZK_HIP(hipGetDevice(&dev));
-  Key key;
-  key.dev = dev;
-  key.log_n = log_n;
-  for (int i = 0; i < 8; ++i) key.w[i] = w.l[i];
-  std::lock_guard<std::mutex> lk(g_mu);
-  PowTables& T = g_tables[key];
-  bool built = false;
-  // on any failure the entry is removed again: a half-built entry (A set, B or a roots table missing) would be taken for
-  // complete by the next call
-  auto fail = [&](hipError_t e, const char* what) {
-    std::fprintf(stderr, "[mi355zk] NTT table build failed (%s): %s\n", what, hipGetErrorString(e));
-    (void)hipStreamSynchronize(st);
-    T.free_all();
-    g_tables.erase(key);
-    return (int)ZK_ERR_DEVICE;
-  };
-  hipError_t e = hipSuccess;
-  if (T.A == nullptr) {
-    built = true;
-    T.h = (log_n + 1) / 2;
-    uint64_t nB = 1ull << T.h, nA = 1ull << (log_n - T.h);
-    if ((e = tab_malloc(&T.A, nA * sizeof(UTab), &T.bytes)) != hipSuccess) return fail(e, "A");
-    if ((e = tab_malloc(&T.B, nB * sizeof(UTab), &T.bytes)) != hipSuccess) return fail(e, "B");
-    hipLaunchKernelGGL(ntt_pow_table_kernel, dim3((unsigned)((nA + 255) / 256)), dim3(256), 0, st, T.A, w, nB, nA);
-    hipLaunchKernelGGL(ntt_pow_table_kernel, dim3((unsigned)((nB + 255) / 256)), dim3(256), 0, st, T.B, w, 1ull, nB);
-    if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch");
-  }
-  if (want_roots) {
-    for (int p = 0; p < nb; ++p) {
-      uint32_t b = bs[p];
-      if (b == 0 || T.roots[b] != nullptr) continue;
-      built = true;
-      uint64_t cnt = 1ull << (b - 1);
-      if ((e = tab_malloc(&T.roots[b], cnt * sizeof(UTab), &T.bytes)) != hipSuccess) return fail(e, "roots");
-      hipLaunchKernelGGL(ntt_pow_table_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, T.roots[b], w, 1ull << (log_n - b), cnt);
-      if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch");
-    }
-  }
-  if (full_log_s != 0 && (T.full == nullptr || T.full_log_s != full_log_s)) {
-    if (T.full) {  // (another split of the same size: only when MI355ZK_NTT_LOGNP changes between calls)
-      if ((e = hipDeviceSynchronize()) != hipSuccess) return fail(e, "sync");
-      (void)hipFree(T.full);
-      T.full = nullptr;
-      T.bytes -= sizeof(UTab) << log_n;
-    }
-    built = true;
-    const uint64_t cnt = 1ull << log_n;
-    if ((e = tab_malloc(&T.full, cnt * sizeof(UTab), &T.bytes)) != hipSuccess) return fail(e, "full");
-    T.full_log_s = full_log_s;
-    hipLaunchKernelGGL(ntt_full_twiddle_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, T.full, T.A, T.B, T.h, full_log_s, cnt);
-    if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch");
-  }
-  if (built && (e = hipStreamSynchronize(st)) != hipSuccess) return fail(e, "sync");  // one-time: tables may be used from other streams later
-  *out = &T;
-  return 0;
-}
-
-// The folded tables of (T's root, pre_g, post_c, post_g) (any of the three may be null, not all): found or built.  Called under g_run_mu;
-// the device pointers are copied out before anybody can evict the entry.  with_full: the two-pass transform's full inter-pass table with
-// everything that is constant per column / per row folded in (ntt_full_folded_kernel); otherwise (2^21 and up, no full table) the small
-// tables of the same split: the first pass's stage table and pre^col, the last pass's (post^stride)^k and post_c * post^(row's first index),
-// and for a transform scaled by post_c alone the low table of the two-level twiddle times post_c.
-// bits[0 .. R): the passes' row lengths (log2), first pass first.
-int build_folded(hipStream_t st, uint32_t log_n, const Fr& omega, PowTables* T, const PowTables* Tpre, const PowTables* Tpost, const Fr* pre_g, const Fr* post_c,
-                 const TwU& post_cu, const Fr* post_g, const uint32_t* bits, int R, bool with_full, PowTables::Folded* out) {
-  std::lock_guard<std::mutex> lk(g_mu);
-  const uint32_t log_first = bits[0], log_last = bits[R - 1];
-  const uint32_t log_s = log_n - log_first;             // columns of the first pass
-  for (const auto& f : T->folded) {
-    if (f.log_s != log_s || f.big != !with_full || f.has_pre != (pre_g != nullptr) || f.has_post_c != (post_c != nullptr) || f.has_post_g != (post_g != nullptr)) continue;
-    if (pre_g && std::memcmp(&f.pre, pre_g, sizeof(Fr)) != 0) continue;
-    if (post_c && std::memcmp(&f.post_c, post_c, sizeof(Fr)) != 0) continue;
-    if (post_g && std::memcmp(&f.post_g, post_g, sizeof(Fr)) != 0) continue;
-    *out = f;
-    return 0;
-  }
-  if (T->folded.size() >= NTT_FOLDED_MAX) {   // the oldest goes, once nothing on the device can still be reading it
-    ZK_HIP(hipDeviceSynchronize());
-    T->folded.front().free_tabs();
-    T->folded.erase(T->folded.begin());
-  }
-  PowTables::Folded f;
-  f.log_s = log_s;
-  f.big = !with_full;
-  if (pre_g) { f.has_pre = true; f.pre = *pre_g; }
-  if (post_c) { f.has_post_c = true; f.post_c = *post_c; }
-  if (post_g) { f.has_post_g = true; f.post_g = *post_g; }
-  const uint64_t cnt = 1ull << log_n, n_first = 1ull << log_first, n_cols = 1ull << log_s, n_last = 1ull << log_last, n_rows_last = cnt >> log_last;
-  hipError_t e = hipSuccess;
-  auto fail = [&](hipError_t err, const char* what) {
-    std::fprintf(stderr, "[mi355zk] NTT folded-table build failed (%s): %s\n", what, hipGetErrorString(err));
-    (void)hipStreamSynchronize(st);
-    f.free_tabs();
-    return (int)ZK_ERR_DEVICE;
-  };
-  auto grid = [](uint64_t c) { return dim3((unsigned)((c + 255) / 256)); };
-  if (pre_g) {
-    // i = x * n_cols + col:  pre^i = (pre^n_cols)^x * pre^col
-    if ((e = tab_malloc(&f.pre_rows, n_first * sizeof(UTab), &f.bytes)) != hipSuccess) return fail(e, "pre rows");
-    hipLaunchKernelGGL(ntt_pow_table_kernel, grid(n_first), dim3(256), 0, st, f.pre_rows, *pre_g, n_cols, n_first);
-    if ((e = tab_malloc(&f.pre_stages, n_first * sizeof(UTab), &f.bytes)) != hipSuccess) return fail(e, "pre stages");
-    hipLaunchKernelGGL(ntt_stage_table_kernel, grid(n_first), dim3(256), 0, st, f.pre_stages, *pre_g, n_cols, omega, n_cols, log_first);
-    if (!with_full) {
-      if ((e = tab_malloc(&f.pre_cols, n_cols * sizeof(UTab), &f.bytes)) != hipSuccess) return fail(e, "pre cols");
-      hipLaunchKernelGGL(ntt_pow_table_kernel, grid(n_cols), dim3(256), 0, st, f.pre_cols, *pre_g, 1ull, n_cols);
-    }
-  }
-  if (post_g) {
-    // K = rb + n_rows_last * k (rb < n_rows_last the row's first output index):  post^K = post^rb * (post^n_rows_last)^k
-    if ((e = tab_malloc(&f.post_rows, n_last * sizeof(UTab), &f.bytes)) != hipSuccess) return fail(e, "post rows");
-    hipLaunchKernelGGL(ntt_pow_table_kernel, grid(n_last), dim3(256), 0, st, f.post_rows, *post_g, n_rows_last, n_last);
-    if (!with_full) {
-      if ((e = tab_malloc(&f.post_rowc, n_rows_last * sizeof(UTab), &f.bytes)) != hipSuccess) return fail(e, "post row constants");
-      hipLaunchKernelGGL(ntt_pow_scaled_table_kernel, grid(n_rows_last), dim3(256), 0, st, f.post_rowc, *post_g, post_c ? *post_c : Fr::one(), n_rows_last);
-    }
-  } else if (post_c && !with_full) {
-    const uint64_t nB = 1ull << T->h;
-    if ((e = tab_malloc(&f.tw_b_scaled, nB * sizeof(UTab), &f.bytes)) != hipSuccess) return fail(e, "scaled twiddles");
-    hipLaunchKernelGGL(ntt_pow_scaled_table_kernel, grid(nB), dim3(256), 0, st, f.tw_b_scaled, omega, *post_c, nB);
-  }
-  if (with_full) {
-    if ((e = tab_malloc(&f.full, cnt * sizeof(UTab), &f.bytes)) != hipSuccess) return fail(e, "full");
-    hipLaunchKernelGGL(ntt_full_folded_kernel, grid(cnt), dim3(256), 0, st, f.full, T->A, T->B, T->h, log_s, cnt,
-                       Tpre ? Tpre->A : nullptr, Tpre ? Tpre->B : nullptr, Tpre ? Tpre->h : 0u, Tpost ? Tpost->A : nullptr,
-                       Tpost ? Tpost->B : nullptr, Tpost ? Tpost->h : 0u, post_cu, post_c != nullptr ? 1 : 0);
-  }
-  if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch");
-  if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(e, "sync");   // one-time: the tables may be used from other streams later
-  T->folded.push_back(f);
-  *out = f;
-  return 0;
-}
-
-struct ScratchBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
-// one scratch array per (device, stream): calls on one stream are ordered by the stream itself, calls on
-// different streams must not share a buffer.  Guarded by g_run_mu (held only while launching).
-std::map<std::pair<int, hipStream_t>, ScratchBuf> g_scratch;
-std::mutex g_run_mu;
 
 std::mutex g_cfg_mu;
 std::map<int, int> g_cfg;  // device -> rc of its one-time kernel configuration
 
+// the device pointer a planned table argument names
+const UTab* ntt_table(NttTab t, const PowTables* T, const PowTables* Tpre, const PowTables* Tpost, const PowTables::Folded& F) {
+  switch (t) {
+    case NTT_TAB_T_A: return T->A;
+    case NTT_TAB_T_B: return T->B;
+    case NTT_TAB_T_FULL: return T->full;
+    case NTT_TAB_TPRE_A: return Tpre->A;
+    case NTT_TAB_TPRE_B: return Tpre->B;
+    case NTT_TAB_TPOST_A: return Tpost->A;
+    case NTT_TAB_TPOST_B: return Tpost->B;
+    case NTT_TAB_F_FULL: return F.full;
+    case NTT_TAB_F_PRE_ROWS: return F.pre_rows;
+    case NTT_TAB_F_PRE_STAGES: return F.pre_stages;
+    case NTT_TAB_F_PRE_COLS: return F.pre_cols;
+    case NTT_TAB_F_POST_ROWS: return F.post_rows;
+    case NTT_TAB_F_POST_ROWC: return F.post_rowc;
+    case NTT_TAB_F_TW_B_SCALED: return F.tw_b_scaled;
+    default: return nullptr;
+  }
+}
+
 }  // namespace
 
-// the tile kernel stages up to 4096 x 36 B = 144 KiB in dynamic LDS (gfx950: 160 KiB per CU)
+// the tile kernels stage up to 4096 x 36 B = 144 KiB in dynamic LDS (gfx950: 160 KiB per CU)
 int ntt_configure() {
   int dev = 0;
   ZK_HIP(hipGetDevice(&dev));
@@ -916,55 +670,20 @@ int ntt_configure() {
   auto it = g_cfg.find(dev);
   if (it != g_cfg.end()) return it->second;
   int rc = ZK_OK;
-  const void* fns[2 * NTT_MAX_LOG_NP + 2] = {};
-#define ZK_NTT_FN(L) fns[L] = reinterpret_cast<const void*>(ntt_pass_kernel<L, false>); fns[NTT_MAX_LOG_NP + L] = reinterpret_cast<const void*>(ntt_pass_kernel<L, true>);
-  ZK_NTT_FN(1) ZK_NTT_FN(2) ZK_NTT_FN(3) ZK_NTT_FN(4) ZK_NTT_FN(5) ZK_NTT_FN(6) ZK_NTT_FN(7) ZK_NTT_FN(8) ZK_NTT_FN(9) ZK_NTT_FN(10)
-  ZK_NTT_FN(11) ZK_NTT_FN(12)
-#undef ZK_NTT_FN
-  const void* wl[5] = {reinterpret_cast<const void*>(ntt_pass_wl_kernel<8>), reinterpret_cast<const void*>(ntt_pass_wl_kernel<9>),
-                       reinterpret_cast<const void*>(ntt_pass_wl_kernel<10>), reinterpret_cast<const void*>(ntt_pass_wl_kernel<11>),
-                       reinterpret_cast<const void*>(ntt_pass_wl_kernel<12>)};
-  for (const void* f : wl)
-    if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) rc = ZK_ERR_DEVICE;
-  for (int l = 1; l <= 2 * NTT_MAX_LOG_NP; ++l) {
-    hipError_t e = hipFuncSetAttribute(fns[l], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      std::fprintf(stderr, "[mi355zk] hipFuncSetAttribute(ntt_pass_kernel, 160 KiB LDS) failed: %s\n", hipGetErrorString(e));
-      rc = ZK_ERR_DEVICE;
+  for (const auto& kind : g_ntt_kernels)
+    for (NttPassKernel fn : kind) {
+      if (fn == nullptr) continue;
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NTT_LDS_BYTES_MAX);
+      if (e != hipSuccess) {
+        std::fprintf(stderr, "[mi355zk] hipFuncSetAttribute(ntt pass kernel, 160 KiB LDS) failed: %s\n", hipGetErrorString(e));
+        rc = ZK_ERR_DEVICE;
+      }
     }
-  }
   g_cfg[dev] = rc;
   return rc;
 }
 
-void ntt_release_all() {
-  std::lock_guard<std::mutex> lk2(g_run_mu);  // (same order as the run path: g_run_mu, then g_mu)
-  std::lock_guard<std::mutex> lk(g_mu);
-  for (auto& kv : g_tables) {
-    (void)hipSetDevice(kv.first.dev);
-    kv.second.free_all();
-  }
-  g_tables.clear();
-  for (auto& kv : g_scratch) {
-    (void)hipSetDevice(kv.first.first);
-    (void)hipFree(kv.second.p);
-  }
-  g_scratch.clear();
-}
-
 int ntt_scale(Fr* d_a, uint32_t log_n, const Fr& c, const Fr* g, hipStream_t st);
-
-// host: a Montgomery form -> the plain integer and its quotient.  The quotient is a 261-round division (~10 us on the host): the few
-// scale factors a process uses (1/m per domain size) are kept.  Called under g_run_mu.
-static TwU to_tw(const Fr& x) {
-  static std::vector<std::pair<Fr, TwU>> memo;
-  for (const auto& e : memo)
-    if (std::memcmp(&e.first, &x, sizeof(Fr)) == 0) return e.second;
-  const TwU t = tw_make(to_canonical(x));
-  if (memo.size() >= 64) memo.clear();
-  memo.emplace_back(x, t);
-  return t;
-}
 
 // d_a: 2^log_n Fr elements on the current device, in place:
 //   a[i] *= pre_g^i (if pre_g)  ->  X[k] = sum_i a[i] * omega^(i*k)  ->  X[k] *= post_c * post_g^k (if given).
@@ -978,6 +697,7 @@ int ntt_run_scaled(Fr* d_a, uint32_t log_n, const Fr& omega, const Fr* pre_g, co
 // then stores, and the load and store phases (~15 of a pass's 47 - 55 us) hide behind nothing.  With the tiles of the next transform queued in
 // the same launch a CU starts loading them while its other workgroup still computes: 2^20 fft 0.105 -> 0.087 ms per transform for batch = 2 .. 3
 // (tools/exp_ntt_streams.py measured the same with one stream per transform: profiles/r05_ntt_batch.txt).
+// What runs is decided by ntt_plan (ntt_plan.hpp); here the plan's tables are found or built, its scratch leased and its passes launched.
 int ntt_run_batch(Fr* const* d_arrays, uint32_t batch, uint32_t log_n, const Fr& omega, const Fr* pre_g, const Fr* post_c, const Fr* post_g, hipStream_t st) {
   if (batch == 0 || batch > NTT_MAX_BATCH || d_arrays == nullptr) return ZK_ERR_BAD_ARGS;
   for (uint32_t t = 0; t < batch; ++t)
@@ -991,24 +711,18 @@ int ntt_run_batch(Fr* const* d_arrays, uint32_t batch, uint32_t log_n, const Fr&
     }
     return 0;
   }
-  Fr* const d_a = d_arrays[0];
-  if (log_n > 30) return ZK_ERR_BAD_ARGS;
-  const uint64_t n = 1ull << log_n;
-  // factor the index: R passes of b[p] bits, b[0] most significant digit (DESIGN.md "NTT")
-  uint32_t b[3];
-  static const char* lognp_env = std::getenv("MI355ZK_NTT_LOGNP");
-  // rows of 2^10 by default; 2^11 / 2^12 where that saves a whole pass: 2^21 and 2^22 in two passes (0.372 -> 0.294 ms, 0.715 ->
-  // 0.57 ms), 2^23 as 12 + 11 (1.36 -> 1.18 ms).  The one- and two-row tiles of those passes move 32- / 64-byte runs; the kernel's
-  // XCD grouping of neighbouring tiles is what makes them pay.  2^24 ran as 12 + 12 in round 2 (2.43 ms); with two 2048-element
-  // workgroups per CU three passes of 2^8-point rows are faster (2.32 ms) than two passes whose 4096-point rows own a CU each.
-  int row_bits = NTT_LOG_NP;
-  if (log_n == 21 || log_n == 22) row_bits = 11;
-  if (log_n == 23) row_bits = 12;
-  if (lognp_env && std::atoi(lognp_env) >= 10 && std::atoi(lognp_env) <= 12) row_bits = std::atoi(lognp_env);
-  int R = (int)((log_n + row_bits - 1) / row_bits);
-  for (int p = 0; p < R; ++p) b[p] = log_n / R + ((uint32_t)p < log_n % R ? 1 : 0);
-
-  int rc = ntt_configure();
+  NttRequest Q;
+  Q.log_n = log_n;
+  Q.batch = batch;
+  Q.pre_g = pre_g != nullptr;
+  Q.post_c = post_c != nullptr;
+  Q.post_g = post_g != nullptr;
+  NttPlan N;
+  // planned first: pure arithmetic, so a refused request (log_n > 30) returns, as it always did, before anything touches the device or the
+  // caches.  (The first call therefore reads every NTT knob, MI355ZK_NTT_TABLES_GB included, here, before the device is touched.)
+  int rc = ntt_plan(Q, ntt_knobs(), &N);
+  if (rc) return rc;
+  rc = ntt_configure();
   if (rc) return rc;
   // held from the table lookup to the last launch: the table cache may be dropped (when full) only while nobody is between
   // "got a table pointer" and "enqueued the kernels that read it"
@@ -1016,217 +730,37 @@ int ntt_run_batch(Fr* const* d_arrays, uint32_t batch, uint32_t log_n, const Fr&
   rc = tables_make_room(3);
   if (rc) return rc;
   PowTables* T = nullptr;
-  static const bool no_full = std::getenv("MI355ZK_NTT_NO_FULL_TW") != nullptr;  // (the two-level product, kept for the comparison in DESIGN.md)
-  const bool full_tw = R == 2 && log_n <= NTT_FULL_TW_MAX_LOG && !no_full;
-  // (round 5) a scaled two-pass transform with a full table takes that table with its scale factors folded in (ntt_full_folded_kernel);
-  // env MI355ZK_NTT_NO_FOLD: the separate products of rounds 1-4, for the A/B
-  static const bool no_fold = std::getenv("MI355ZK_NTT_NO_FOLD") != nullptr;
-  const bool fold = full_tw && !no_fold && (pre_g || post_c || post_g);
-  // ... and from 2^21 on (no full table; every pass a full tile of the wave-local kernel) the small tables of the same split
-  const bool fold_big = !full_tw && R >= 2 && log_n >= 21 && !no_fold && (pre_g || post_c || post_g);
-  rc = build_pow_tables(st, log_n, omega, true, b, R, &T, (full_tw && !fold) ? b[1] : 0);
-  if (rc) return rc;
   PowTables* Tpre = nullptr;
   PowTables* Tpost = nullptr;
-  if (pre_g) { rc = build_pow_tables(st, log_n, *pre_g, false, nullptr, 0, &Tpre); if (rc) return rc; }
-  if (post_g) { rc = build_pow_tables(st, log_n, *post_g, false, nullptr, 0, &Tpost); if (rc) return rc; }
+  rc = build_pow_tables(st, log_n, omega, true, N.b, N.R, &T, N.full_log_s);
+  if (rc) return rc;
+  if (N.want_tpre) { rc = build_pow_tables(st, log_n, *pre_g, false, nullptr, 0, &Tpre); if (rc) return rc; }
+  if (N.want_tpost) { rc = build_pow_tables(st, log_n, *post_g, false, nullptr, 0, &Tpost); if (rc) return rc; }
   const TwU post_cu = post_c ? to_tw(*post_c) : (post_g ? to_tw(Fr::one()) : TwU{FrU::zero(), FrU::zero()});   // (neither: post == 3 multiplies by nothing)
   PowTables::Folded F;
-  if (fold || fold_big) { rc = build_folded(st, log_n, omega, T, Tpre, Tpost, pre_g, post_c, post_cu, post_g, b, R, fold, &F); if (rc) return rc; }
-  const UTab* k_full = fold ? F.full : T->full;
-  const UTab* k_preA = fold ? F.pre_rows : (Tpre ? Tpre->A : nullptr);
-  const UTab* k_preB = (!fold && Tpre) ? Tpre->B : nullptr;
-  const UTab* k_postA = fold ? F.post_rows : (Tpost ? Tpost->A : nullptr);
-  const UTab* k_postB = (!fold && Tpost) ? Tpost->B : nullptr;
+  if (N.want_folded) { rc = build_folded(st, log_n, omega, T, Tpre, Tpost, pre_g, post_c, post_cu, post_g, N.b, N.R, N.fold, &F); if (rc) return rc; }
   static const int slot_pass = prof_slot("ntt_pass");
-
   Fr* scratch = nullptr;
-  if (R > 1) {
+  if (N.want_scratch) {
     int dev = 0;
     ZK_HIP(hipGetDevice(&dev));
-    // (one buffer per stream a caller has ever used: bounded -- a caller that makes a stream per call must not pin a buffer per
-    // stream for ever.  Past 16 streams on this device everything is dropped once the device is idle; g_run_mu keeps other
-    // transforms from being enqueued meanwhile.)
-    if (g_scratch.find(std::make_pair(dev, st)) == g_scratch.end()) {
-      size_t mine = 0;
-      for (auto& kv : g_scratch) mine += kv.first.first == dev ? 1 : 0;
-      if (mine >= 16) {
-        ZK_HIP(hipDeviceSynchronize());
-        for (auto it = g_scratch.begin(); it != g_scratch.end();) {
-          if (it->first.first != dev) { ++it; continue; }
-          (void)hipFree(it->second.p);
-          it = g_scratch.erase(it);
-        }
-      }
-    }
-    ScratchBuf& sb = g_scratch[std::make_pair(dev, st)];
-    const size_t scratch_bytes = n * sizeof(Fr) * batch;
-    if (sb.bytes < scratch_bytes) {
-      if (sb.p) {
-        ZK_HIP(hipStreamSynchronize(st));  // earlier passes on this stream may still read the old buffer
-        ZK_HIP(hipFree(sb.p));
-      }
-      sb.p = nullptr;
-      sb.bytes = 0;
-      ZK_HIP(hipMalloc(&sb.p, scratch_bytes));
-      sb.bytes = scratch_bytes;
-    }
-    scratch = (Fr*)sb.p;
+    rc = scratch_for(dev, st, (sizeof(Fr) << log_n) * batch, &scratch);
+    if (rc) return rc;
   }
 
-  // tile size: 2048 elements (72 KiB of LDS, 512 lanes with a group of four each: TWO workgroups per CU, whose barriers tie eight
-  // waves instead of sixteen and whose load / compute / store phases may drift apart) for transforms of 2^20 and more; rows of 2^12
-  // are a tile of their own.  Round 2 measured 2048-element tiles 2-5 % SLOWER -- but with radix-2 stages on 1024-lane workgroups,
-  // of which the registers (125 VGPRs) admit one per CU: that was never two workgroups per CU.  With a lane per group of four:
-  // 2^20 0.1474 -> 0.1443 ms (ifft 0.1418 -> 0.1386), 2^22 0.569 -> 0.544 (ifft 0.536 -> 0.498).  env MI355ZK_NTT_TILE = 4096 / 2048 / 1024.
-  static const char* env_tile = std::getenv("MI355ZK_NTT_TILE");
-  uint64_t tile_elems = log_n >= 20 ? 2048 : NTT_TILE_ELEMS;
-  if (env_tile && (std::atoi(env_tile) == 2048 || std::atoi(env_tile) == 4096 || std::atoi(env_tile) == 1024)) tile_elems = (uint64_t)std::atoi(env_tile);
-  // S[p] = prod_{q>p} N_q ; Tm[p] = prod_{q<p} N_q
-  uint64_t S[3], Tm[3];
-  for (int p = 0; p < R; ++p) {
-    S[p] = 1;
-    Tm[p] = 1;
-    for (int q = p + 1; q < R; ++q) S[p] <<= b[q];
-    for (int q = 0; q < p; ++q) Tm[p] <<= b[q];
-  }
-
-  for (int p = 0; p < R; ++p) {
-    NttPassParams P{};
-    P.log_np = b[p];
-    const uint64_t np = 1ull << b[p];
-    const Fr* src;
-    Fr* dst;
-    if (R == 1) { src = d_a; dst = d_a; }
-    else if (p == 0) { src = d_a; dst = scratch; }
-    else if (p == R - 1) { src = scratch; dst = d_a; }
-    else { src = scratch; dst = scratch; }
+  for (int p = 0; p < N.R; ++p) {
+    const NttPass& pass = N.pass[p];
     NttBatch BP{};
     for (uint32_t t = 0; t < batch; ++t) {
-      BP.in[t] = (src == d_a) ? d_arrays[t] : scratch + (uint64_t)t * n;
-      BP.out[t] = (dst == d_a) ? d_arrays[t] : scratch + (uint64_t)t * n;
+      BP.in[t] = pass.src == NTT_BUF_ARRAY ? d_arrays[t] : scratch + ((uint64_t)t << log_n);
+      BP.out[t] = pass.dst == NTT_BUF_ARRAY ? d_arrays[t] : scratch + ((uint64_t)t << log_n);
     }
-    uint64_t tiles;
-    if (p < R - 1 || R == 1) {
-      // columns: G adjacent low positions share a tile
-      uint64_t G = tile_elems / np;
-      if (G < 1) G = 1;
-      if (G > S[p]) G = S[p];
-      while (G > 1 && n / (np * G) < 256) G >>= 1;  // small transforms: prefer >= 256 tiles (one per CU) over wide tiles
-      P.g = (uint32_t)G;
-      P.in_xs = P.out_xs = S[p];
-      P.in_gs = P.out_gs = 1;
-      P.tiles_lo = S[p] / G;
-      P.in_hi_stride = P.out_hi_stride = np * S[p];
-      P.in_lo_stride = P.out_lo_stride = G;
-      P.load_x_fastest = (G == 1);
-      P.tw_mul = (R == 1) ? 0 : Tm[p];
-      P.tw_h = T->h;
-      P.tw_full = (full_tw && p == 0) ? 1u : 0u;  // (p == 0 of R == 2: Tm = 1, hi = 0, so the output position is k * S + col)
-      tiles = Tm[p] * P.tiles_lo;
-    } else {
-      // last pass: G rows with adjacent k_1; hi = k_1 group, lo = middle digit (R == 3) else 0
-      uint64_t N1 = 1ull << b[0];
-      uint64_t G = tile_elems / np;
-      if (G < 1) G = 1;
-      if (G > N1) G = N1;
-      while (G > 1 && n / (np * G) < 256) G >>= 1;
-      P.g = (uint32_t)G;
-      P.in_xs = 1;
-      P.in_gs = S[0];
-      P.out_xs = n >> b[p];
-      P.out_gs = 1;
-      uint64_t mid = (R == 3) ? (1ull << b[1]) : 1;
-      P.tiles_lo = mid;
-      P.in_hi_stride = G * S[0];
-      P.in_lo_stride = np;      // middle digit k_2 sits at stride S[1] = N_3 = np
-      P.out_hi_stride = G;
-      P.out_lo_stride = N1;     // k_2 * T_2 = k_2 * N_1
-      P.load_x_fastest = 1;
-      P.tw_mul = 0;
-      tiles = (N1 / G) * mid;
-    }
-    P.batch = batch;
-    P.tiles = tiles;
-    static const bool no_pair = std::getenv("MI355ZK_NTT_NOPAIR") != nullptr;
-    static const char* pair_env = std::getenv("MI355ZK_NTT_PAIR");
-    static const bool pair_all = std::getenv("MI355ZK_NTT_PAIR_ALL") != nullptr;
-    // (narrow tiles only: with 128-byte runs and more the grouping is neutral -- measured with MI355ZK_NTT_PAIR_ALL)
-    P.xcd_pair = ((P.g <= 2 || pair_all) && tiles % 256 == 0 && !no_pair) ? (pair_env ? (uint32_t)std::atoi(pair_env) : 5u) : 0u;
-    if (p == 0 && Tpre) { P.pre = fold ? 2 : 1; P.pre_h = Tpre->h; }   // (fold + the wave-local kernel: 3, below)
-    if (p == R - 1) {
-      if (fold) P.post = Tpost ? 4 : 3;    // post_c (and post_g^k1) sit in the folded table
-      else P.post = Tpost ? 2 : (post_c ? 1 : 3);
-      P.post_h = Tpost ? Tpost->h : 0;
-    }
-    uint32_t pitch = (uint32_t)np;
-    size_t lds_bytes = (size_t)P.g * pitch * 36;
-    uint32_t threads = (uint32_t)((P.g * np) / 2);
-    if (threads > NTT_THREADS) threads = NTT_THREADS;
-    if (threads < 64) threads = 64;
+    const UTab* tab[NTT_ARGS];
+    for (uint32_t a = 0; a < NTT_ARGS; ++a) tab[a] = ntt_table(pass.tab[a], T, Tpre, Tpost, F);
     prof_begin(slot_pass, st);
-    // (one instantiation per row length: static stage loops.  Radix-4 register butterflies for full tiles (transforms of 2^20 and
-    // more), radix-2 for the narrow tiles of short transforms, whose passes are latency-bound and want two butterflies per lane
-    // rather than half the lanes idle; env MI355ZK_NTT_RADIX = 2 / 4 forces one)
-    static const char* radix_env = std::getenv("MI355ZK_NTT_RADIX");
-    // a full tile (>= 2048 elements): a lane per group of four
-    const bool r4 = radix_env ? std::atoi(radix_env) == 4 : (uint64_t)P.g * np >= 2048;
-    if (r4) {
-      threads = (uint32_t)((P.g * np) / 4);
-      if (threads > NTT_THREADS) threads = NTT_THREADS;
-      if (threads < 64) threads = 64;
-    }
-    // full tiles of rows of >= 256 elements: the wave-local kernel (round 5; env MI355ZK_NTT_WAVELOCAL=0: the barrier-per-pair kernel, for the A/B)
-    static const bool no_wl = std::getenv("MI355ZK_NTT_WAVELOCAL") != nullptr && std::getenv("MI355ZK_NTT_WAVELOCAL")[0] == '0';
-    const bool wl_kernel = r4 && !no_wl && b[p] >= 8 && (uint64_t)P.g * np == 4ull * threads;
-    static const bool no_stage_fold = std::getenv("MI355ZK_NTT_NO_STAGE_FOLD") != nullptr;
-    const UTab* k_preA_p = k_preA;
-    const UTab* k_preB_p = k_preB;
-    const UTab* k_postA_p = k_postA;
-    const UTab* k_postB_p = k_postB;
-    const UTab* k_twB_p = T->B;
-    if (p == 0 && Tpre && fold && wl_kernel && !no_stage_fold) { P.pre = 3; k_preA_p = F.pre_stages; }
-    if (fold_big && wl_kernel) {
-      if (p == 0 && Tpre) { P.pre = 4; k_preA_p = F.pre_stages; k_preB_p = F.pre_cols; }
-      if (p == R - 1 && Tpost) { P.post = 5; k_postA_p = F.post_rows; k_postB_p = F.post_rowc; }
-    }
-    // a transform scaled by post_c alone: the pass before the last multiplies it in with its twiddle, the last pass by nothing
-    // (decided for both passes together: the last pass must be able to drop the product whichever kernel runs it -- post == 3 is in both)
-    if (fold_big && post_c && !Tpost) {
-      if (p == R - 2) k_twB_p = F.tw_b_scaled;
-      if (p == R - 1) P.post = 3;
-    }
-#define ZK_NTT_LAUNCH_WL(L)                                                                                                                \
-  case L:                                                                                                                                  \
-    hipLaunchKernelGGL((ntt_pass_wl_kernel<L>), dim3((unsigned)(tiles * batch)), dim3(threads), lds_bytes, st, src, dst, P, T->roots[b[p]], T->A,      \
-                       k_twB_p, k_preA_p, k_preB_p, k_postA_p, k_postB_p,    \
-                       post_cu, k_full, BP);                                                                                                  \
-    break;
-    if (wl_kernel) {
-      switch (b[p]) {
-        ZK_NTT_LAUNCH_WL(8) ZK_NTT_LAUNCH_WL(9) ZK_NTT_LAUNCH_WL(10) ZK_NTT_LAUNCH_WL(11) ZK_NTT_LAUNCH_WL(12)
-        default: return ZK_ERR_BAD_ARGS;
-      }
-    } else {
-#define ZK_NTT_LAUNCH(L)                                                                                                                   \
-  case L:                                                                                                                                  \
-    if (r4)                                                                                                                                \
-      hipLaunchKernelGGL((ntt_pass_kernel<L, true>), dim3((unsigned)(tiles * batch)), dim3(threads), lds_bytes, st, src, dst, P, T->roots[b[p]], T->A, \
-                         k_twB_p, k_preA, k_preB, k_postA, k_postB,  \
-                         post_cu, k_full, BP);                                                                                                \
-    else                                                                                                                                   \
-      hipLaunchKernelGGL((ntt_pass_kernel<L, false>), dim3((unsigned)(tiles * batch)), dim3(threads), lds_bytes, st, src, dst, P, T->roots[b[p]], T->A, \
-                         k_twB_p, k_preA, k_preB, k_postA, k_postB,  \
-                         post_cu, k_full, BP);                                                                                                \
-    break;
-    switch (b[p]) {
-      ZK_NTT_LAUNCH(1) ZK_NTT_LAUNCH(2) ZK_NTT_LAUNCH(3) ZK_NTT_LAUNCH(4) ZK_NTT_LAUNCH(5) ZK_NTT_LAUNCH(6) ZK_NTT_LAUNCH(7) ZK_NTT_LAUNCH(8)
-      ZK_NTT_LAUNCH(9) ZK_NTT_LAUNCH(10) ZK_NTT_LAUNCH(11) ZK_NTT_LAUNCH(12)
-      default: return ZK_ERR_BAD_ARGS;
-    }
-    }
-#undef ZK_NTT_LAUNCH
-#undef ZK_NTT_LAUNCH_WL
+    hipLaunchKernelGGL(g_ntt_kernels[pass.kind][pass.P.log_np], dim3(pass.grid), dim3(pass.threads), pass.lds_bytes, st, BP.in[0], BP.out[0], pass.P,
+                       T->roots[pass.P.log_np], tab[NTT_ARG_TW_A], tab[NTT_ARG_TW_B], tab[NTT_ARG_PRE_A], tab[NTT_ARG_PRE_B], tab[NTT_ARG_POST_A],
+                       tab[NTT_ARG_POST_B], post_cu, tab[NTT_ARG_TW_F], BP);
     ZK_HIP(hipGetLastError());
     prof_end(slot_pass, st);
   }
