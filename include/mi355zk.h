@@ -415,6 +415,13 @@ enum mi355zk_devop {
   MI355ZK_DEVOP_G2_JAC_DOUBLE, MI355ZK_DEVOP_G2_JAC_ADD_TAB, MI355ZK_DEVOP_G2_JAC_TAB_PSI,
   MI355ZK_DEVOP_COUNT
 };
+/* Ops whose vectors live in a test file of their own (the enum above is, name by name, the table of tests/field_edge_vectors.py); the codes go on
+ * from MI355ZK_DEVOP_COUNT.  G1_ADD_AFFINE_PAIR: xyzzu_from_affine_pair (curveu.hpp), how a bucket opens -- x1, y1, x2, y2 (Fp words), negate1,
+ * negate2  ->  the accumulator (36 words), xyzzu_to_r of it (32); U-form over Fq, both builds.  tests/test_gpu_pair_start_op.py. */
+enum mi355zk_devop_more {
+  MI355ZK_DEVOP_G1_ADD_AFFINE_PAIR = MI355ZK_DEVOP_COUNT,
+  MI355ZK_DEVOP_END
+};
 #define MI355ZK_DEVOP_CHAIN 0x100
 int mi355zk_selftest_dev_op(int op, int which, const uint32_t *in, size_t in_words_per_case, uint32_t *out, size_t out_words_per_case, size_t n_cases);
 

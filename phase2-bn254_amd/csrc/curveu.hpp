@@ -135,6 +135,74 @@ ZK_HD void xyzzu_add_mixed(XYZZU<PR>& acc, const Fp<PR>& x2s, const Fp<PR>& y2s,
   acc.zzz = zzz3;
 }
 
+// 32 * a for an N-form a < 2p, N-form again: a 5-bit shift across the 29-bit limbs (l[8] < 2^23 going in, < 2^28 coming out)
+template <class PR>
+ZK_HD FpU<PR> u_shl5_lt2p(const FpU<PR>& a) {
+  FpU<PR> r;
+  r.l[0] = (a.l[0] << 5) & U_MASK;
+#pragma unroll
+  for (int i = 1; i < 8; ++i) r.l[i] = ((a.l[i] << 5) & U_MASK) | (a.l[i - 1] >> 24);
+  r.l[8] = (a.l[8] << 5) | (a.l[7] >> 24);
+  return r;
+}
+
+// acc = (+/-)(x1, y1) + (+/-)(x2, y2): how a bucket OPENS.  Both points affine, canonical memory-format coordinates (2^256 domain), neither
+// the identity.  The empty-accumulator branch of xyzzu_add_mixed followed by a full mixed addition costs 2 * 162 + 1467 = 1791 mads; the
+// sum of two affine points needs no ZZ1 / ZZZ1 products at all, and the domains close WITHOUT a constant product when the result is
+// taken with Z = P * 2^-5 (any Z != 0 names the same point: X = x Z^2, Y = y Z^3, ZZ = Z^2, ZZZ = Z^3):
+//     P = x2 - x1, R = y2 - y1 as loaded                            P * 2^256,  R * 2^256
+//     ZZ  = u_mul(P, 32 P)      = P^2 * 2^(256 + 261 - 261)         = (P^2 * 2^-10) * 2^266          the 2^266 domain of ZZ
+//     ZZZ = u_mul(P, ZZ)        = P^3 * 2^251                       = (P^3 * 2^-15) * 2^266          the 2^266 domain of ZZZ
+//     Q   = u_mul(x1, ZZ)       = x1 P^2 * 2^251                    = (x1 P^2 * 2^-10) * 2^261       the 2^261 domain of X
+//     RR  = u_sqr(R)            = R^2 * 2^251                                                        the same; PPP * 2^251 IS ZZZ
+//     X   = RR - ZZZ - 2 Q      = (R^2 - P^3 - 2 x1 P^2) * 2^-10 * 2^261
+//     Y   = u_mul2(R, Q - X, -y1, ZZZ) = (R (Q' - X') - y1 P^3) * 2^(256 + 251 - 261) = (...) * 2^-15 * 2^261
+// (32 P is a shift: P < 2p, so 32 P < 64p stays inside u_mul's bounds.)  3 * 162 + 126 + 243 = 855 mads: 936 fewer per populated bucket.
+// Result under the accumulator invariant: X < 6p, Y < 2p, ZZ < 2p, ZZZ < 2p, N-form; infinity is literal-zero ZZ.
+// Equal x (equal memory words: the coordinates are canonical): the same signed y doubles (xyzzu_double_affine, as xyzzu_add_mixed does),
+// anything else is the opposite point: infinity.
+template <class PR>
+ZK_HD XYZZU<PR> xyzzu_from_affine_pair(const Fp<PR>& x1s, const Fp<PR>& y1s, bool neg1, const Fp<PR>& x2s, const Fp<PR>& y2s, bool neg2) {
+  const FpU<PR> x1 = u_from_std(x1s), x2 = u_from_std(x2s);     // < p, N
+  FpU<PR> y1 = u_from_std(y1s), y2 = u_from_std(y2s);           // < p, N
+  {
+    const FpU<PR> n1 = u_sub<1, 1>(FpU<PR>::zero(), y1);         // p - y1 in (0, p], N
+    const FpU<PR> n2 = u_sub<1, 1>(FpU<PR>::zero(), y2);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+      y1.l[i] = neg1 ? n1.l[i] : y1.l[i];                       // signed y in (0, p): y != 0
+      y2.l[i] = neg2 ? n2.l[i] : y2.l[i];
+    }
+  }
+  XYZZU<PR> res = XYZZU<PR>::zero();                            // (ONE exit: see xyzzr_add_quad)
+  if (x1s == x2s) {
+    // P == 0: same point -> double (ec.rs:483-485); opposite -> infinity (ec.rs:487).  Canonical coordinates (the precondition: see
+    // accumulate_run in msm_impl.hpp): equal values are equal words, and equal limbs.  (The test is on the loaded words on purpose: on
+    // P or on ZZ == 0 mod p, as xyzzu_add_mixed has it, the rare branch holds more state across the branch and msm_accumulate_kernel
+    // goes from 125 to 136 VGPRs -- the fourth wave.)
+    uint32_t d = 0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) d |= y1.l[i] ^ y2.l[i];
+    if (d == 0) res = xyzzu_double_affine(x2, y2);
+  } else {
+    const FpU<PR> p = u_sub<1, 1>(x2, x1);                      // x2 + p - x1 in (0, 2p), N
+    const FpU<PR> r = u_sub<1, 1>(y2, y1);                      // y1 <= p;  R in (0, 2p), N
+    const FpU<PR> p32 = u_shl5_lt2p(p);                         // < 64p, N, l[8] < 2^28
+    const FpU<PR> zz = u_mul(p, p32);                           // 2 * 64 c + 1 < 1.77p  (invariant ZZ < 2p)
+    const FpU<PR> zzz = u_mul(p, zz);                           // 2 * 1.77 c + 1 < 1.03p  (invariant ZZZ < 2p)
+    const FpU<PR> q = u_mul(x1, zz);                            // < 1.02p
+    const FpU<PR> rr = u_sqr(r);                                // 4c + 1 < 1.03p
+    const FpU<PR> t = u_add(zzz, u_dbl(q));                     // < 3.07p <= 4p, limbs < 3 * 2^29
+    res.x = u_sub<4, 3>(rr, t);                                 // < 5.03p  (invariant X < 6p)
+    const FpU<PR> d = u_sub<8, 1>(q, res.x);                    // < 9.02p, N
+    const FpU<PR> ny1 = u_sub<1, 1>(FpU<PR>::zero(), y1);       // p - y1 in (0, p], N
+    res.y = u_mul2(r, d, ny1, zzz);                             // R*D - y1*PPP: (2 * 9.02 + 1.03) c + 1 < 1.12p  (invariant Y < 2p)
+    res.zz = zz;                                                // P != 0 mod p, so ZZ != 0 mod p: never the zero limbs of infinity
+    res.zzz = zzz;
+  }
+  return res;
+}
+
 // accumulator -> memory-format XYZZ (canonical coordinates, 2^256 domain); infinity -> all zero
 template <class PR>
 ZK_HD XYZZ<Fp<PR>> xyzzu_to_std(const XYZZU<PR>& a) {

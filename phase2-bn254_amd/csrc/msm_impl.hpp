@@ -1007,7 +1007,17 @@ struct BucketAcc<Fq2> { using type = XYZZU2; };
 
 // acc += the signed points of one index list.  The accumulator is the caller's: zero for a fresh bucket, xyzzu_from_r(record)
 // for a bucket carried from an earlier chunk of a streamed multiexp (msm_accumulate_kernel<.., CARRY>).
-template <class F, bool A4 = false>
+// The bases are raw affine records with CANONICAL coordinates (< p), as every producer of such records writes them (the decoders of
+// codec.hip, batch_normalize, the reference's own vectors); nothing checks that at upload, and xyzzu_add_mixed / xyzzu_from_affine_pair
+// state it as their precondition: their lazy subtractions are sized for it, and the pair start finds two points with the same x by
+// comparing the loaded words (a record holding x + p instead of x would be added as a different x: a wrong bucket, no error).
+// PAIR_START (G1): a run of at least two entries that meets an EMPTY accumulator opens with xyzzu_from_affine_pair (curveu.hpp: 855 mads
+// for the first two points where the copy into the empty accumulator and a full mixed addition cost 1791) and the loop takes over at the
+// third entry.  The gathers keep their order: point 2 is issued as ever, point 3 is in flight before the pair arithmetic starts.  An
+// identity record among the first two leaves everything to the loop, from entry j, with its skip / error report.  The CARRY launches
+// do not set it: a lane whose carried record is not empty would enter the loop two entries behind its neighbours and the A4 reload
+// below would no longer be uniform over the wave.
+template <class F, bool A4 = false, bool PAIR_START = false>
 __device__ __forceinline__ typename BucketAcc<F>::type accumulate_run(typename BucketAcc<F>::type acc, const Affine<F>* __restrict__ bases, const uint32_t* __restrict__ vals,
                                                uint32_t j, uint32_t e, uint32_t stride, bool skip_zero, unsigned long long* __restrict__ err_base) {
   // the all-zero record is the point at infinity (no curve point has y == 0).  skip_zero (dense mode, powersoftau's
@@ -1028,13 +1038,47 @@ __device__ __forceinline__ typename BucketAcc<F>::type accumulate_run(typename B
     v = vals[j];
   }
   Affine<F> p = load_affine(bases + (v & ~SIGN_BIT));
-  for (;;) {
+  bool more_left = true;
+  if constexpr (PAIR_START && std::is_same<F, Fq>::value) {
+    if (acc.is_zero() && j + stride < e) {
+      uint4 q2 = q;
+      const uint32_t j2 = j + stride, j3 = j2 + stride;
+      const bool more3 = j3 < e;
+      uint32_t v2, v3 = 0;
+      if constexpr (A4) {
+        q2.x = q2.y; q2.y = q2.z; q2.z = q2.w;   // j is a multiple of 4 and the stride is 1: entries 2 and 3 are in the group loaded above
+        v2 = q2.x;
+      } else {
+        v2 = vals[j2];
+      }
+      const Affine<F> p2 = load_affine(bases + (v2 & ~SIGN_BIT));
+      Affine<F> p3 = p2;
+      if constexpr (A4) {
+        q2.x = q2.y; q2.y = q2.z; q2.z = q2.w;
+        v3 = q2.x;
+        if (more3) p3 = load_affine(bases + (v3 & ~SIGN_BIT));
+      } else if (more3) {
+        v3 = vals[j3];
+        p3 = load_affine(bases + (v3 & ~SIGN_BIT));
+      }
+      if (!p.y.is_zero() && !p2.y.is_zero()) {
+        acc = xyzzu_from_affine_pair(p.x, p.y, (v & SIGN_BIT) != 0, p2.x, p2.y, (v2 & SIGN_BIT) != 0);
+        more_left = more3;
+        q = q2;
+        v = v3;
+        p = p3;
+        j = j3;
+      }
+    }
+  }
+  if (more_left) for (;;) {
     const uint32_t jn = j + stride;
     const bool more = jn < e;
     uint32_t vn = 0;
     Affine<F> pn = p;
     if constexpr (A4) {
-      if ((jn & 3u) == 0) {  // uniform over the wave: every lane started on a multiple of 4
+      if ((jn & 3u) == 0) {  // uniform over the wave: every lane started on a multiple of 4, or (PAIR_START) two entries further -- all lanes with
+                             // a second entry alike, save one that met an identity record among its first two (an error, or dense mode's rare skip)
         if (more) q = *reinterpret_cast<const uint4*>(vals + jn);
       } else {
         q.x = q.y; q.y = q.z; q.z = q.w;
@@ -1137,7 +1181,7 @@ __global__ void __launch_bounds__(MSM_HEAVY_LANES) msm_accumulate_heavy_kernel(c
     const uint32_t e = j0 + seg < last[b] ? j0 + seg : last[b];
     U a = U::zero();
     if (j0 + threadIdx.x < e)   // an R-domain record (curveu.hpp) is what every consumer of bucket sums works on: its register form here
-      a = xyzzr_load(xyzzu_to_r(accumulate_run<F>(U::zero(), bases, vals, j0 + threadIdx.x, e, blockDim.x, skip_zero != 0, err_base)));
+      a = xyzzr_load(xyzzu_to_r(accumulate_run<F, false, true>(U::zero(), bases, vals, j0 + threadIdx.x, e, blockDim.x, skip_zero != 0, err_base)));
     a = wave_sum_quads(a, sh);   // (round 4: the 6-level tree on quad additions)
     if (threadIdx.x == 0) store_vec(seg_sums + item, xyzzr_store(a));
     __syncthreads();
@@ -1191,7 +1235,7 @@ __global__ void __launch_bounds__(256) msm_accumulate_kernel(const Affine<F>* __
   //  its two products are not measurable.  Adding the record at the END by a full addition instead was 1.2 x slower per launch: ~3000
   //  instructions executed once per wave run from a cold instruction cache.)
   if constexpr (CARRY) acc = xyzzu_from_r(load_vec(buckets + b));
-  store_vec(buckets + b, xyzzu_to_r(accumulate_run<F, A4>(acc, bases, vals, j, e, 1, skip_zero != 0, err_base)));
+  store_vec(buckets + b, xyzzu_to_r(accumulate_run<F, A4, !CARRY>(acc, bases, vals, j, e, 1, skip_zero != 0, err_base)));
 }
 // G2 with >= 2^19 buckets: the same kernel at TWO waves per SIMD.  With the rare doubling in U-form (xyzzu2_double_affine) the Fq2 loop
 // needs 262 registers -- it took 256 + 147 with the saturated-limb doubling inlined -- and at a budget of 256 the seven that do not

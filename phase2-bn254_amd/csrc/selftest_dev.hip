@@ -21,7 +21,7 @@ struct DevBuf {   // freed on every exit
 int selftest_dev_op(int op_flags, int which, const uint32_t* in, size_t in_words, uint32_t* out, size_t out_words, size_t n) {
   const bool chain = (op_flags & MI355ZK_DEVOP_CHAIN) != 0;
   const int op = op_flags & ~MI355ZK_DEVOP_CHAIN;
-  if (op < 0 || op >= MI355ZK_DEVOP_COUNT || (which != 0 && which != 1)) return ZK_ERR_BAD_ARGS;
+  if (op < 0 || op >= MI355ZK_DEVOP_END || (which != 0 && which != 1)) return ZK_ERR_BAD_ARGS;
   const selftest_plain::DevOpShape S = selftest_plain::devop_shape(op);
   if (S.in_words == 0 || in_words != (size_t)S.in_words || out_words != (size_t)S.out_words) return ZK_ERR_BAD_ARGS;
   if ((which == 1 && !S.fr) || (chain && !S.chain)) return ZK_ERR_BAD_ARGS;

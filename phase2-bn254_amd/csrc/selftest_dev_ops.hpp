@@ -61,6 +61,7 @@ constexpr DevOpShape devop_shape(int op) {
     case MI355ZK_DEVOP_G1_RECORD_TRIP: return {36, 100, 1, false, true};     // acc -> xyzzu_to_r, xyzzu_from_r of it, xyzzr_store(xyzzr_load) of it
     case MI355ZK_DEVOP_G1_RADD_QUAD: return {72, 68, 4, false, true};
     case MI355ZK_DEVOP_G1_PAIR_ADD_MIXED: return {53, 34, 2, false, true};   // -> this lane's (a, z) and its two record coordinates
+    case MI355ZK_DEVOP_G1_ADD_AFFINE_PAIR: return {34, 68, 1, false, true};   // x1, y1, x2, y2, negate1, negate2  ->  acc, xyzzu_to_r(acc)
     case MI355ZK_DEVOP_G2_DOUBLE_AFFINE: return {32, 72, 1, false, false};
     case MI355ZK_DEVOP_G2_DOUBLE: return {72, 72, 1, false, false};
     case MI355ZK_DEVOP_G2_ADD_MIXED: return {105, 136, 1, false, false};
@@ -262,7 +263,11 @@ __device__ __forceinline__ void devop_run(const uint32_t* in, uint32_t* out, uin
     group_op<G1Ops, OP - MI355ZK_DEVOP_G1_DOUBLE_AFFINE>(in, out, lane);
   else if constexpr (OP >= MI355ZK_DEVOP_G2_DOUBLE_AFFINE && OP <= MI355ZK_DEVOP_G2_PAIR_ADD_MIXED)
     group_op<G2Ops, OP - MI355ZK_DEVOP_G2_DOUBLE_AFFINE>(in, out, lane);
-  else if constexpr (OP == MI355ZK_DEVOP_G1_JAC_DOUBLE) jac_op<G1Ops, 0>(in, out);
+  else if constexpr (OP == MI355ZK_DEVOP_G1_ADD_AFFINE_PAIR) {
+    const XYZZU<FqParams> acc = xyzzu_from_affine_pair(st_ld<Fq>(in), st_ld<Fq>(in + 8), in[32] != 0, st_ld<Fq>(in + 16), st_ld<Fq>(in + 24), in[33] != 0);
+    st_st(out, acc);
+    st_st(out + 36, xyzzu_to_r(acc));
+  } else if constexpr (OP == MI355ZK_DEVOP_G1_JAC_DOUBLE) jac_op<G1Ops, 0>(in, out);
   else if constexpr (OP == MI355ZK_DEVOP_G1_JAC_ADD_MIXED) jac_op<G1Ops, 1>(in, out);
   else if constexpr (OP == MI355ZK_DEVOP_G1_JAC_ADD_TAB) jac_op<G1Ops, 2>(in, out);
   else if constexpr (OP == MI355ZK_DEVOP_G2_JAC_DOUBLE) jac_op<G2Ops, 0>(in, out);
@@ -302,7 +307,7 @@ int devop_dispatch(int op, int which, const uint32_t* d_in, uint32_t* d_out, uin
 
 // d_in: blocks * 256 cases, d_out: room for as many results
 inline int devop_launch(int op, int which, const uint32_t* d_in, uint32_t* d_out, uint32_t blocks) {
-  return devop_dispatch(op, which, d_in, d_out, blocks, std::make_integer_sequence<int, MI355ZK_DEVOP_COUNT>{});
+  return devop_dispatch(op, which, d_in, d_out, blocks, std::make_integer_sequence<int, MI355ZK_DEVOP_END>{});
 }
 
 }  // namespace ZK_ST_NS
