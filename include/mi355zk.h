@@ -34,6 +34,8 @@
  *   2  UnexpectedEof:      the bases ran out                                      (source.rs:46-48,62-64)
  *   3  bad arguments (NULL pointer, log_n > 28 = PolynomialDegreeTooLarge domain.rs:66-79, sizes >= 2^31, an exponent
  *      >= 2^254, i.e. not a canonical FrRepr: mi355zk_last_error_index() names it)
+ *  4 .. 8  the GroupDecodingError of a wire record (the point codecs and the accumulator entry points below), 5 = NotInSubgroup
+ *  9  PointAtInfinity: a record of an accumulator file is the point at infinity (the accumulator entry points)
  *  <0  device failure (details on stderr).  There is NO CPU fallback inside the library.
  * When both error kinds are present the one at the lowest exponent index is reported (the reference's
  * answer depends on thread scheduling there; see oracle/tmpl_multiexp.h).
@@ -57,6 +59,7 @@ extern "C" {
 #define MI355ZK_ERR_UNEXPECTED_IDENTITY 1
 #define MI355ZK_ERR_UNEXPECTED_EOF 2
 #define MI355ZK_ERR_BAD_ARGS 3
+#define MI355ZK_ERR_POINT_AT_INFINITY 9 /* 4 .. 8 are the GroupDecodingError kinds of the point codecs */
 #define MI355ZK_ERR_DEVICE (-1)
 
 /* EvaluationDomain operations (domain.rs:154-203) for mi355zk_bn254_fr_domain_op[_dev] */
@@ -540,6 +543,40 @@ int mi355zk_bn254_g2_batch_exp(uint8_t *out_affine, const uint8_t *bases_affine,
  * is an addition for callers that handle untrusted G2 data, not a drop-in for anything.  Synchronises `stream`. */
 int mi355zk_bn254_g2_subgroup_check_dev(const void *d_points_affine, size_t n, void *stream, long long *bad_index);
 int mi355zk_selftest_g2_in_subgroup(const uint64_t affine_pt[16]);   /* host run of the same test: 1 / 0 */
+
+/* ---- powers-of-tau accumulator files, streamed: WIRE records in host memory on both sides (typically mmap'ed file ranges: pageable, `in`
+ * may be read-only), decoded and encoded on the device, worked off in pieces so that device memory does not grow with n.  `in` / `out` hold
+ * n records of 64 / 128 B (G1 / G2 uncompressed) or 32 / 64 B (compressed), the encodings of the point codecs above.
+ * piece: records per device piece (0 = 2^18).  Piece i + 1 is uploaded while piece i runs its kernels and piece i - 1 is downloaded (two
+ * buffer sets, a copy and a compute stream of the calling thread's current device).  Device memory of a call, with P = min(piece, n):
+ *   transform    2 P (in_record + out_record + 2 raw + 32) B + batch_exp's own scratch for P points
+ *   power_pairs  2 P (in_record + raw + out_record or 0 + 1) B + P 32 B of exponents + the dense multiexp's pools for P points
+ * (raw = 64 / 128 B), never a function of n.
+ * accumulator_transform: out[i] = encode((coeff * tau^(first + i)) * decode(in[i])) -- the body of BatchedAccumulator::transform for one
+ *   vector range (powersoftau/src/batched_accumulator.rs:1187-1290: read_chunk, taupowers, batch_exp, the not-infinity assertion,
+ *   write_chunk).  tau, coeff: canonical FrRepr (< r, else 3); coeff == NULL is 1.  checked: into_affine instead of into_affine_unchecked.
+ *   mode: 0 or MI355ZK_G2_TRUSTED_SUBGROUP (as batch_exp; ignored for G1).  in and out may not overlap.
+ * accumulator_power_pairs: decodes n records and returns the Jacobian sums s = sum_{i < n-1} rho_(first+i) v[i] and
+ *   sx = sum_{i < n-1} rho_(first+i) v[i+1], rho_g = scalar g of the stream (key, stream_id) of fr_random above: power_pairs
+ *   (powersoftau/src/utils.rs:133-135) over one chunk.  The scalar index is global, so the sums over chunks that overlap by one record add up
+ *   (mi355zk_bn254_g{1,2}_add) to exactly what merge_pairs_random gives for the whole vector, however it is cut.  n == 1 gives two
+ *   identities.  out_uncompressed (may be NULL): the n records re-encoded uncompressed in the same pass (`decompress`,
+ *   batched_accumulator.rs:543-617).  check_subgroup (G2 only): every record must pass the test of mi355zk_bn254_g2_subgroup_check_dev.
+ * Both: 3 = a NULL pointer, n >= 2^31, piece == 1; n == 0 succeeds and does nothing.  A record the decoder refuses returns the decoder's code
+ * (4, 6, 7, 8), a G2 record outside the subgroup under check_subgroup 5, a point at infinity on input -- or on transform's output --
+ * MI355ZK_ERR_POINT_AT_INFINITY (read_points_chunk :938-983, :1176); *err_index (may be NULL) is then the lowest index, within the call, of
+ * the pieces up to the first that fails, and -1 otherwise.  On any non-zero return the contents of `out` / `out_uncompressed` are unspecified
+ * (the caller discards the file).  Synchronous; re-entrant from several host threads. */
+int mi355zk_bn254_g1_accumulator_transform(uint8_t *out, const uint8_t *in, size_t n, uint64_t first, const uint64_t tau[4], const uint64_t coeff[4],
+                                           int in_compressed, int out_compressed, int checked, uint32_t mode, size_t piece, long long *err_index);
+int mi355zk_bn254_g2_accumulator_transform(uint8_t *out, const uint8_t *in, size_t n, uint64_t first, const uint64_t tau[4], const uint64_t coeff[4],
+                                           int in_compressed, int out_compressed, int checked, uint32_t mode, size_t piece, long long *err_index);
+int mi355zk_bn254_g1_accumulator_power_pairs(const uint8_t *in, size_t n, int compressed, int checked, int check_subgroup, const uint32_t key[8],
+                                             uint64_t stream_id, uint64_t first, uint8_t *out_uncompressed, size_t piece, uint64_t out_s[12],
+                                             uint64_t out_sx[12], long long *err_index);
+int mi355zk_bn254_g2_accumulator_power_pairs(const uint8_t *in, size_t n, int compressed, int checked, int check_subgroup, const uint32_t key[8],
+                                             uint64_t stream_id, uint64_t first, uint8_t *out_uncompressed, size_t piece, uint64_t out_s[24],
+                                             uint64_t out_sx[24], long long *err_index);
 
 /* ---- the pairing e: G1 x G2 -> GT (Engine::miller_loop + final_exponentiation, pairing/src/bn256/mod.rs:57-226) in its batched form: many
  * independent pairing PRODUCTS in one call -- every same_ratio of a verify_transformation (powersoftau/src/utils.rs:151-159), the four

@@ -9,6 +9,8 @@ Layout:
   keys.py         hash_to_g2, the key pairs and public-key records of both ceremonies (host work on single points)
   verify.py       the ceremony steps and their checks: contribute_mpc_parameters, verify_contribution, verify_mpc_parameters,
                   contribute_response, verify_transform, next_challenge -- one pairing launch per verification
+  stream.py       powers-of-tau files streamed through the device in bounded memory: batches, calculate_hash_file, new_constrained,
+                  compute_constrained, verify_transform_constrained (file to file, mmap'ed; the in-memory flows of verify.py are the yardstick)
   prover.py       the caller of the path: groth16 create_proof (prover.rs:202-343) over the device library
   ceremony.py     the ceremony-side callers (batch_exp, merge_pairs, QAP evaluation, point FFT, codecs, file containers)
   bellman.py      host-side mirror of the reference's interface for this path:
@@ -17,7 +19,7 @@ Layout:
 The directory name carries a hyphen (it is the reference's name); import it through the
 repo-root shim module `phase2_bn254_amd`.
 """
-from . import bellman, ceremony, circom, generator, keys, lib, pairing, prover, shard, verify  # noqa: F401
+from . import bellman, ceremony, circom, generator, keys, lib, pairing, prover, shard, stream, verify  # noqa: F401
 from .bellman import (  # noqa: F401
     DensityTracker,
     EvaluationDomain,
@@ -31,6 +33,13 @@ from .bellman import (  # noqa: F401
     multiexp,
     pin_bases,
     unpin_bases,
+)
+from .stream import (  # noqa: F401
+    batches,
+    calculate_hash_file,
+    compute_constrained,
+    new_constrained,
+    verify_transform_constrained,
 )
 from .verify import (  # noqa: F401
     VerificationError,

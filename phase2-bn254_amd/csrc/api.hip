@@ -803,6 +803,30 @@ int mi355zk_bn254_g2_batch_exp_dev(void* d_out_affine, const void* d_bases_affin
   });
 }
 
+// powers-of-tau accumulator files, streamed (accumulator_stream.hip)
+int mi355zk_bn254_g1_accumulator_transform(uint8_t* out, const uint8_t* in, size_t n, uint64_t first, const uint64_t tau[4], const uint64_t coeff[4],
+                                           int in_compressed, int out_compressed, int checked, uint32_t mode, size_t piece, long long* err_index) {
+  return abi_guard([&]() -> int { return accumulator_transform<1>(out, in, n, first, tau, coeff, in_compressed, out_compressed, checked, mode, piece, err_index); });
+}
+int mi355zk_bn254_g2_accumulator_transform(uint8_t* out, const uint8_t* in, size_t n, uint64_t first, const uint64_t tau[4], const uint64_t coeff[4],
+                                           int in_compressed, int out_compressed, int checked, uint32_t mode, size_t piece, long long* err_index) {
+  return abi_guard([&]() -> int { return accumulator_transform<2>(out, in, n, first, tau, coeff, in_compressed, out_compressed, checked, mode, piece, err_index); });
+}
+int mi355zk_bn254_g1_accumulator_power_pairs(const uint8_t* in, size_t n, int compressed, int checked, int check_subgroup, const uint32_t key[8],
+                                             uint64_t stream_id, uint64_t first, uint8_t* out_uncompressed, size_t piece, uint64_t out_s[12],
+                                             uint64_t out_sx[12], long long* err_index) {
+  return abi_guard([&]() -> int {
+    return accumulator_power_pairs<1>(in, n, compressed, checked, check_subgroup, key, stream_id, first, out_uncompressed, piece, out_s, out_sx, err_index);
+  });
+}
+int mi355zk_bn254_g2_accumulator_power_pairs(const uint8_t* in, size_t n, int compressed, int checked, int check_subgroup, const uint32_t key[8],
+                                             uint64_t stream_id, uint64_t first, uint8_t* out_uncompressed, size_t piece, uint64_t out_s[24],
+                                             uint64_t out_sx[24], long long* err_index) {
+  return abi_guard([&]() -> int {
+    return accumulator_power_pairs<2>(in, n, compressed, checked, check_subgroup, key, stream_id, first, out_uncompressed, piece, out_s, out_sx, err_index);
+  });
+}
+
 // host-side group helpers (joining per-GPU partial sums, normalising results)
 int mi355zk_bn254_g1_add(uint64_t acc_xyz[12], const uint64_t other_xyz[12]) {
   return abi_guard([&]() -> int {

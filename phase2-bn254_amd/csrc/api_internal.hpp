@@ -3,6 +3,7 @@
 //   host_entry.hip  the host-buffer entry points: Source / Density plan, bases cache, streamed upload, multi-GPU cells
 //   scalar_mul.hip  the scalar-multiplication kernels and their launchers: batch_exp / batch_mul / window-table build / G2 membership
 //   fr_random.hip   the random exponents of merge_pairs generated on the device (chacha.hpp: the generator shared with the host)
+//   accumulator_stream.hip  powers-of-tau files streamed through the device: wire records in host memory on both sides, bounded pieces
 //   fixed_base.hip  one base, a window table of its multiples, no doublings per scalar (fixed_base.hpp: the program shared with the host)
 //   (msm_g1.hip, msm_g2.hip, ntt.hip, point_fft*.hip, codec.hip, field_ops.hip, records.hip: the kernels behind the functions declared below)
 #pragma once
@@ -46,6 +47,8 @@ int point_fft_g1(void* d_points, uint32_t log_n, const Fr& omega, bool scale, co
 // codec.hip
 int codec_decode(int group, void* d_out, const void* d_in, size_t n, int compressed, int checked, hipStream_t st, long long* err_index);
 int codec_encode(int group, void* d_out, const void* d_in, size_t n, int compressed, hipStream_t st);
+// the decode kernel alone, enqueued on `st`: *d_err (set to ~0 by the caller, on the stream) takes the minimum of (index << 8 | code) over the refused records
+int codec_decode_enqueue(int group, void* d_out, const void* d_in, size_t n, int compressed, int checked, hipStream_t st, unsigned long long* d_err);
 // point_fft_g2.hip
 int point_fft_g2(void* d_points, uint32_t log_n, const Fr& omega, bool scale, const Fr& scale_canon, hipStream_t st, bool trusted_subgroup);
 
@@ -133,6 +136,17 @@ int batch_exp_host(uint8_t* out, const uint8_t* bases, const uint64_t* scalars, 
 template <int GROUP>
 int dense_host(const uint8_t* v1, const uint8_t* v2, const uint64_t* rho, size_t n, uint64_t* out_s, uint64_t* out_sx, const FrRandomStream* rnd = nullptr);
 int ntt_host(uint64_t* a, uint32_t log_n, int op, const uint64_t* omega);
+// accumulator_stream.hip (include/mi355zk.h: mi355zk_bn254_g{1,2}_accumulator_transform / _power_pairs)
+template <int GROUP>
+int accumulator_transform(uint8_t* out, const uint8_t* in, size_t n, uint64_t first, const uint64_t* tau, const uint64_t* coeff, int in_compressed,
+                          int out_compressed, int checked, uint32_t mode, size_t piece, long long* err_index);
+template <int GROUP>
+int accumulator_power_pairs(const uint8_t* in, size_t n, int compressed, int checked, int check_subgroup, const uint32_t* key, uint64_t stream_id,
+                            uint64_t first, uint8_t* out_uncompressed, size_t piece, uint64_t* out_s, uint64_t* out_sx, long long* err_index);
+extern template int accumulator_transform<1>(uint8_t*, const uint8_t*, size_t, uint64_t, const uint64_t*, const uint64_t*, int, int, int, uint32_t, size_t, long long*);
+extern template int accumulator_transform<2>(uint8_t*, const uint8_t*, size_t, uint64_t, const uint64_t*, const uint64_t*, int, int, int, uint32_t, size_t, long long*);
+extern template int accumulator_power_pairs<1>(const uint8_t*, size_t, int, int, int, const uint32_t*, uint64_t, uint64_t, uint8_t*, size_t, uint64_t*, uint64_t*, long long*);
+extern template int accumulator_power_pairs<2>(const uint8_t*, size_t, int, int, int, const uint32_t*, uint64_t, uint64_t, uint8_t*, size_t, uint64_t*, uint64_t*, long long*);
 int h_poly_host(uint64_t* h, const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t len, uint32_t log_n, uint32_t flags);
 template <class F>
 int sparse_matvec(void* d_out, const void* d_bases, size_t n_bases, const uint32_t* d_row_ptr, const uint32_t* d_col, const void* d_coeffs,

@@ -302,19 +302,32 @@ int run_decode(size_t n, hipStream_t st, long long* err_index, DecodeLaunch&& la
 
 }  // namespace
 
-int codec_decode(int group, void* d_out, const void* d_in, size_t n, int compressed, int checked, hipStream_t st, long long* err_index) {
+static const CodecConsts& codec_consts() {
   static const CodecConsts K = make_consts();
+  return K;
+}
+static void launch_decode(int group, void* d_out, const void* d_in, size_t n, int compressed, int checked, hipStream_t st, unsigned long long* d_err) {
+  const CodecConsts& K = codec_consts();
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-  return run_decode(n, st, err_index, [&](unsigned long long* d_err) {
-    const uint32_t* in = (const uint32_t*)d_in;
-    if (group == 1) {
-      if (compressed) hipLaunchKernelGGL(g1_decode_kernel<true>, grid, block, 0, st, in, (G1Affine*)d_out, n, checked, K, d_err);
-      else hipLaunchKernelGGL(g1_decode_kernel<false>, grid, block, 0, st, in, (G1Affine*)d_out, n, checked, K, d_err);
-    } else {
-      if (compressed) hipLaunchKernelGGL(g2_decode_kernel<true>, grid, block, 0, st, in, (G2Affine*)d_out, n, checked, K, d_err);
-      else hipLaunchKernelGGL(g2_decode_kernel<false>, grid, block, 0, st, in, (G2Affine*)d_out, n, checked, K, d_err);
-    }
-  });
+  const uint32_t* in = (const uint32_t*)d_in;
+  if (group == 1) {
+    if (compressed) hipLaunchKernelGGL(g1_decode_kernel<true>, grid, block, 0, st, in, (G1Affine*)d_out, n, checked, K, d_err);
+    else hipLaunchKernelGGL(g1_decode_kernel<false>, grid, block, 0, st, in, (G1Affine*)d_out, n, checked, K, d_err);
+  } else {
+    if (compressed) hipLaunchKernelGGL(g2_decode_kernel<true>, grid, block, 0, st, in, (G2Affine*)d_out, n, checked, K, d_err);
+    else hipLaunchKernelGGL(g2_decode_kernel<false>, grid, block, 0, st, in, (G2Affine*)d_out, n, checked, K, d_err);
+  }
+}
+
+int codec_decode(int group, void* d_out, const void* d_in, size_t n, int compressed, int checked, hipStream_t st, long long* err_index) {
+  return run_decode(n, st, err_index, [&](unsigned long long* d_err) { launch_decode(group, d_out, d_in, n, compressed, checked, st, d_err); });
+}
+
+int codec_decode_enqueue(int group, void* d_out, const void* d_in, size_t n, int compressed, int checked, hipStream_t st, unsigned long long* d_err) {
+  if (n == 0) return ZK_OK;
+  launch_decode(group, d_out, d_in, n, compressed, checked, st, d_err);
+  ZK_HIP(hipGetLastError());
+  return ZK_OK;
 }
 
 int codec_encode(int group, void* d_out, const void* d_in, size_t n, int compressed, hipStream_t st) {

@@ -16,6 +16,8 @@
 #define ZK_ERR_UNEXPECTED_IDENTITY 1  // bellman/src/source.rs:50-52
 #define ZK_ERR_UNEXPECTED_EOF 2       // bellman/src/source.rs:46-48,62-64
 #define ZK_ERR_BAD_ARGS 3
+#define ZK_ERR_NOT_IN_SUBGROUP 5       // GroupDecodingError::NotInSubgroup (4, 6, 7, 8: the codes of codec.hip)
+#define ZK_ERR_POINT_AT_INFINITY 9     // powersoftau/src/utils.rs DeserializationError::PointAtInfinity
 #define ZK_ERR_DEVICE (-1)            // any HIP failure; message on stderr
 
 namespace zk {

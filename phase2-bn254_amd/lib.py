@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("MI355ZK_SO") or os.path.join(_HERE, "libmi355zk.so")
 
 OK, ERR_UNEXPECTED_IDENTITY, ERR_UNEXPECTED_EOF, ERR_BAD_ARGS, ERR_DEVICE = 0, 1, 2, 3, -1
+ERR_POINT_AT_INFINITY = 9   # MI355ZK_ERR_POINT_AT_INFINITY (the accumulator entry points; 4 .. 8 are ceremony.GroupDecodingError.KINDS)
 OP_FFT, OP_IFFT, OP_COSET_FFT, OP_ICOSET_FFT = 0, 1, 2, 3
 MSM_SCALARS_MONTGOMERY = 1
 NO_FLAG, PIN_TABLES = (1 << 64) - 1, 1   # MI355ZK_NO_FLAG (inf_off: no infinity flag byte) / MI355ZK_PIN_TABLES (include/mi355zk.h)
@@ -134,7 +135,11 @@ SIGNATURES = {
     "mi355zk_bn254_g2_batch_exp": (_i, [_vp, _vp, _vp, _sz, _i]),
     "mi355zk_bn254_g1_batch_exp_dev": (_i, [_vp, _vp, _vp, _sz, _i, _vp]),
     "mi355zk_bn254_g2_batch_exp_dev": (_i, [_vp, _vp, _vp, _sz, _i, _vp]),
-    "mi355zk_bn254_g2_subgroup_check_dev": (_i, [_vp, _sz, _vp, C.POINTER(C.c_longlong)]),
+    "mi355zk_bn254_g1_accumulator_transform": (_i, [_vp, _vp, _sz, C.c_uint64, _vp, _vp, _i, _i, _i, _u32, _sz, C.POINTER(C.c_longlong)]),
+    "mi355zk_bn254_g2_accumulator_transform": (_i, [_vp, _vp, _sz, C.c_uint64, _vp, _vp, _i, _i, _i, _u32, _sz, C.POINTER(C.c_longlong)]),
+    "mi355zk_bn254_g1_accumulator_power_pairs": (_i, [_vp, _sz, _i, _i, _i, _u32p, C.c_uint64, C.c_uint64, _vp, _sz, _vp, _vp, C.POINTER(C.c_longlong)]),
+    "mi355zk_bn254_g2_accumulator_power_pairs": (_i, [_vp, _sz, _i, _i, _i, _u32p, C.c_uint64, C.c_uint64, _vp, _sz, _vp, _vp, C.POINTER(C.c_longlong)]),
+    "mi355zk_bn254_g2_subgroup_check_dev":(_i, [_vp, _sz, _vp, C.POINTER(C.c_longlong)]),
     "mi355zk_selftest_g2_in_subgroup": (_i, [_vp]),
     "mi355zk_bn254_pairing_product_dev": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "mi355zk_bn254_gt_is_one_dev": (_i, [_vp, _vp, _sz, _vp]),

@@ -282,6 +282,31 @@ def next_challenge(response_bytes, power: int, device=None):
 _ACC_VECTORS = ("tau_g1", "tau_g2", "alpha_g1", "beta_g1", "beta_g2")
 
 
+def _decide_transform(device, pk, digest: bytes, before, after, powers):
+    """The eleven same_ratio checks and the two byte equalities of verify_transform in ONE pairing launch, read in the reference's order.
+    before / after: {vector: its first records} (two of tau_g1 and tau_g2 are used, one of the others; device tensors or host records);
+    powers: {vector: power_pairs of the whole vector as a pair of affine host records}.  Shared by the in-memory flow below and the
+    file-to-file flow of stream.py, which gets `powers` from chunked sums."""
+    g2_s = {name: keys.compute_g2_s(digest, pk[f"{name}_g1_s"], pk[f"{name}_g1_s_{name}"], i) for i, name in enumerate(("tau", "alpha", "beta"))}
+    ratios = _Ratios(device)
+    for name in ("tau", "alpha", "beta"):
+        ratios.add(f"{name} proof of knowledge", (pk[f"{name}_g1_s"], pk[f"{name}_g1_s_{name}"]), (g2_s[name], pk[f"{name}_g2"]))
+    ratios.add("tau change", (before["tau_g1"][1], after["tau_g1"][1]), (g2_s["tau"], pk["tau_g2"]))
+    ratios.add("alpha change", (before["alpha_g1"][0], after["alpha_g1"][0]), (g2_s["alpha"], pk["alpha_g2"]))
+    ratios.add("beta change", (before["beta_g1"][0], after["beta_g1"][0]), (g2_s["beta"], pk["beta_g2"]))
+    ratios.add("beta_g2 change", (before["beta_g1"][0], after["beta_g1"][0]), (before["beta_g2"][0], after["beta_g2"][0]))
+    tau_g1_pair, tau_g2_pair = (after["tau_g1"][0], after["tau_g1"][1]), (after["tau_g2"][0], after["tau_g2"][1])
+    ratios.add("tau_g1 powers", powers["tau_g1"], tau_g2_pair)
+    ratios.add_g2_first("tau_g2 powers", powers["tau_g2"], tau_g1_pair)
+    ratios.add("alpha_g1 powers", powers["alpha_g1"], tau_g2_pair)
+    ratios.add("beta_g1 powers", powers["beta_g1"], tau_g2_pair)
+    flags = {"tau_g1[0]": np.array_equal(keys._host(after["tau_g1"][0], 8), ceremony.G1_ONE_RAW),
+             "tau_g2[0]": np.array_equal(keys._host(after["tau_g2"][0], 16), ceremony.G2_ONE_RAW)}
+    _first_failure(("tau proof of knowledge", "alpha proof of knowledge", "beta proof of knowledge", "tau_g1[0]", "tau_g2[0]", "tau change",
+                    "alpha change", "beta change", "beta_g2 change", "tau_g1 powers", "tau_g2 powers", "alpha_g1 powers", "beta_g1 powers"),
+                   ratios.run(), flags)
+
+
 def verify_transform(before, after, public_key, digest: bytes, key: bytes = None, check_g2_subgroup: bool = True) -> bool:
     """verify_transform (batched_accumulator.rs:182-272): `after` is `before` (two dicts as ceremony.read_accumulator returns them)
     transformed by the holder of `public_key` (keys.read_public_key), for the 64-byte transcript `digest` (the hash of the challenge
@@ -294,23 +319,9 @@ def verify_transform(before, after, public_key, digest: bytes, key: bytes = None
     _fail_unless(after["tau_g1"].shape[0] >= 2 and after["tau_g2"].shape[0] >= 2, "tau powers length")
     pk = public_key
     _subgroup([after["tau_g2"], after["beta_g2"], before["beta_g2"], pk["tau_g2"], pk["alpha_g2"], pk["beta_g2"]], check_g2_subgroup)
-    g2_s = {name: keys.compute_g2_s(digest, pk[f"{name}_g1_s"], pk[f"{name}_g1_s_{name}"], i) for i, name in enumerate(("tau", "alpha", "beta"))}
     ex = _Exponents(key)
-    ratios = _Ratios(after["tau_g1"].device)
-    for name in ("tau", "alpha", "beta"):
-        ratios.add(f"{name} proof of knowledge", (pk[f"{name}_g1_s"], pk[f"{name}_g1_s_{name}"]), (g2_s[name], pk[f"{name}_g2"]))
-    ratios.add("tau change", (before["tau_g1"][1], after["tau_g1"][1]), (g2_s["tau"], pk["tau_g2"]))
-    ratios.add("alpha change", (before["alpha_g1"][0], after["alpha_g1"][0]), (g2_s["alpha"], pk["alpha_g2"]))
-    ratios.add("beta change", (before["beta_g1"][0], after["beta_g1"][0]), (g2_s["beta"], pk["beta_g2"]))
-    ratios.add("beta_g2 change", (before["beta_g1"][0], after["beta_g1"][0]), (before["beta_g2"][0], after["beta_g2"][0]))
-    tau_g1_pair, tau_g2_pair = (after["tau_g1"][0], after["tau_g1"][1]), (after["tau_g2"][0], after["tau_g2"][1])
-    ratios.add("tau_g1 powers", _powers(after["tau_g1"], ex), tau_g2_pair)
-    ratios.add_g2_first("tau_g2 powers", _powers(after["tau_g2"], ex), tau_g1_pair)
-    ratios.add("alpha_g1 powers", _powers(after["alpha_g1"], ex), tau_g2_pair)
-    ratios.add("beta_g1 powers", _powers(after["beta_g1"], ex), tau_g2_pair)
-    flags = {"tau_g1[0]": np.array_equal(keys._host(after["tau_g1"][0], 8), ceremony.G1_ONE_RAW),
-             "tau_g2[0]": np.array_equal(keys._host(after["tau_g2"][0], 16), ceremony.G2_ONE_RAW)}
-    _first_failure(("tau proof of knowledge", "alpha proof of knowledge", "beta proof of knowledge", "tau_g1[0]", "tau_g2[0]", "tau change",
-                    "alpha change", "beta change", "beta_g2 change", "tau_g1 powers", "tau_g2 powers", "alpha_g1 powers", "beta_g1 powers"),
-                   ratios.run(), flags)
+    powers = {name: _powers(after[name], ex) for name in ("tau_g1", "tau_g2", "alpha_g1", "beta_g1")}
+    _decide_transform(after["tau_g1"].device, pk, digest, {"tau_g1": before["tau_g1"][:2], "alpha_g1": before["alpha_g1"][:1],
+                      "beta_g1": before["beta_g1"][:1], "beta_g2": before["beta_g2"][:1]},
+                      {name: after[name][:2] for name in _ACC_VECTORS}, powers)
     return True
