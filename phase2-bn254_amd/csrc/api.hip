@@ -548,7 +548,7 @@ int mi355zk_msm_window_bits_groups(size_t n_scalars, uint32_t window_groups, int
     return (int)c;
   });
 }
-// (test hook) digit extraction of one scalar on the host: see msm_selftest_digits in msm_g1.hip
+// (test hook) digit extraction of one scalar on the host: see msm_selftest_digits in msm_partition.hip
 int mi355zk_selftest_msm_digits(size_t n_scalars, uint32_t window_groups, const uint32_t scalar[8], uint32_t w_start, uint32_t w_stop, int direct,
                                 int32_t* digits, uint32_t* geom) {
   return abi_guard([&]() -> int {

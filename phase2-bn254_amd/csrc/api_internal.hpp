@@ -5,7 +5,7 @@
 //   fr_random.hip   the random exponents of merge_pairs generated on the device (chacha.hpp: the generator shared with the host)
 //   accumulator_stream.hip  powers-of-tau files streamed through the device: wire records in host memory on both sides, bounded pieces
 //   fixed_base.hip  one base, a window table of its multiples, no doublings per scalar (fixed_base.hpp: the program shared with the host)
-//   (msm_g1.hip, msm_g2.hip, ntt.hip, point_fft*.hip, codec.hip, field_ops.hip, records.hip: the kernels behind the functions declared below)
+//   (msm_g1.hip, msm_g2.hip, msm_partition.hip, ntt.hip, point_fft*.hip, codec.hip, field_ops.hip, records.hip: the kernels behind the functions declared below)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,7 +25,7 @@ int ntt_run_batch(Fr* const* d_arrays, uint32_t batch, uint32_t log_n, const Fr&
 int ntt_scale(Fr* d_a, uint32_t log_n, const Fr& c, const Fr* g, hipStream_t st);
 void ntt_release_all();
 int ntt_configure();
-// msm_g1.hip, msm_g2.hip (the kernels: msm_impl.hpp; msm_device: msm_host.hpp)
+// msm_g1.hip, msm_g2.hip (the kernels: msm_impl.hpp; msm_device: msm_host.hpp); the geometry and self-test functions: msm_partition.hip
 int msm_g1_device(const void* d_bases, uint64_t n_bases, uint64_t base_offset, const void* d_scalars, uint64_t n, const uint32_t* d_density,
                   const uint32_t* d_dprefix, hipStream_t st, uint64_t out_xyz[12], long long* err_index, uint32_t wgroups, uint32_t wgroup, bool scalars_mont,
                   MsmChunks* chunks, uint64_t table_stride = 0, uint32_t table_c = 0);

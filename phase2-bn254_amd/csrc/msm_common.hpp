@@ -1,12 +1,11 @@
 #pragma once
-// What the Pippenger kernels (msm_impl.hpp) and the host-side planner (msm_plan.hpp) share: the geometry structs that travel as
-// kernel arguments and the compile-time limits both sides size things by.  No HIP header: the planner and the join compile and run
-// without a device (tests/cpp/test_msm_host.cpp).
+// What the Pippenger kernels (msm_partition.hip, msm_impl.hpp) and the host-side planner (msm_plan.hpp) share: the geometry structs
+// that travel as kernel arguments and the compile-time limits both sides size things by.  No HIP header: the planner and the join
+// compile and run without a device (tests/cpp/test_msm_host.cpp).  The structs are ordinary zk:: types, not per-unit copies: they
+// cross the boundary between msm_partition.hip and the two units that include msm_host.hpp.
 #include <stdint.h>
 
 namespace zk {
-
-namespace {  // one copy per translation unit (msm_g1.hip / msm_g2.hip): compiled in parallel
 
 constexpr uint32_t SIGN_BIT = 0x80000000u;
 
@@ -29,7 +28,7 @@ struct MsmGeom {
   uint32_t rshift;
 };
 
-// partition (msm_impl.hpp, section 2)
+// partition (msm_partition.hip, section 2)
 constexpr uint32_t MSM_SIZE_BINS = 4096;   // bins of the counting sort that orders the buckets by size (3b)
 constexpr uint32_t PART_THREADS = 1024;
 constexpr uint32_t PART_MAX_ST = 16384;       // super-tile: scalars per pass-A histogram dump = elements per pass-B workgroup
@@ -67,7 +66,5 @@ constexpr uint32_t MSM_FINAL_MAX = 1024;  // (2048 and 8192 measured in round 2:
 constexpr uint32_t MSM_TREE_SLICE = 512;
 constexpr uint32_t MSM_MAX_LEVELS = 8;
 constexpr uint32_t MSM_MAX_JOBS = MSM_MAX_LEVELS + 24;
-
-}  // namespace
 
 }  // namespace zk

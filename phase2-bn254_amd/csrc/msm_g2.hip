@@ -1,4 +1,5 @@
-// G2 instantiation of the Pippenger pipeline (kernels: msm_impl.hpp, see there for the design; host driver: msm_host.hpp).
+// G2 instantiation of the Pippenger pipeline (kernels: msm_impl.hpp, see there for the design; host driver: msm_host.hpp; the stages that
+// do not depend on the group: msm_partition.hip).
 #include "msm_host.hpp"
 
 namespace zk {

@@ -1,7 +1,8 @@
 #pragma once
 // Host driver of the Pippenger pipeline: msm_device = plan (msm_plan.hpp) -> lease a workspace (msm_pools.hpp) -> per chunk
-// digits / partition / accumulate -> per base set reduce, copy back and join (msm_join.hpp); segsum_device, the segmented sum that
-// reuses the accumulation.  The kernels are msm_impl.hpp's; msm_g1.hip / msm_g2.hip include this file once each.
+// digits / partition (msm_partition.hip, compiled once for both groups) / accumulate -> per base set reduce, copy back and join
+// (msm_join.hpp); segsum_device, the segmented sum that reuses the accumulation.  The kernels launched from here are msm_impl.hpp's,
+// the ones that depend on the group; msm_g1.hip / msm_g2.hip include this file once each.
 #include <atomic>
 #include <chrono>
 #include <cstring>
@@ -12,222 +13,56 @@
 
 #include "msm_impl.hpp"
 #include "msm_join.hpp"
+#include "msm_partition.hpp"
 #include "msm_plan.hpp"
 #include "msm_pools.hpp"
 
 namespace zk {
 
-// multiexps inside msm_device per device, G1 and G2 together (defined in msm_g1.hip): a call that has the device to itself may
-// take every register of a SIMD (the two-wave G2 accumulation); one of the prover's eight concurrent calls leaves room for the others
-extern std::atomic<int> g_msm_inflight[16];
-
 namespace {
 
-// hist: MSM_SIZE_BINS words, zeroed by the caller
-inline void msm_order_by_size(const uint32_t* first, const uint32_t* last, uint32_t n_buckets, uint32_t* hist, uint32_t* order,
-                              uint32_t* sizes_sorted, hipStream_t st) {
-  uint32_t hb = (n_buckets + 4095) / 4096;
-  hipLaunchKernelGGL(msm_size_hist_kernel, dim3(hb < 1024 ? hb : 1024), dim3(1024), 0, st, first, last, n_buckets, hist);
-  hipLaunchKernelGGL(msm_size_scan_kernel, dim3(1), dim3(1024), 0, st, hist);
-  hipLaunchKernelGGL(msm_size_scatter_kernel, dim3((n_buckets + 1024 * MSM_SCATTER_PER - 1) / (1024 * MSM_SCATTER_PER)), dim3(1024), 0, st, first,
-                     last, n_buckets, hist, order, sizes_sorted);
-}
-
-// the partition kernels use up to the whole 160 KiB of LDS (dynamic): raise the limit once per device
+// What is left to configure per group: the tree kernel keeps 256 register-form sums in LDS (72 KiB for G2, above the 64 KiB a kernel
+// gets without asking).  Once per device, after the shared partition kernels (msm_partition.hip: part_configure(dev)).
 std::mutex g_part_cfg_mu;
-std::map<std::pair<int, int>, int> g_part_cfg;
+std::map<int, int> g_part_cfg;
 template <class F>
 int part_configure(int dev) {
   std::lock_guard<std::mutex> lk(g_part_cfg_mu);
-  const std::pair<int, int> key(dev, (int)sizeof(F));
-  auto it = g_part_cfg.find(key);
+  auto it = g_part_cfg.find(dev);
   if (it != g_part_cfg.end()) return it->second;
-  int rc = ZK_OK;
-  // (the tree kernel keeps 256 register-form sums in LDS: 72 KiB for G2, above the 64 KiB a kernel gets without asking)
-  std::vector<const void*> fns = {reinterpret_cast<const void*>(msm_scatter_kernel), reinterpret_cast<const void*>(msm_bucket_kernel),
-                                  reinterpret_cast<const void*>(msm_bigbin_place_kernel), reinterpret_cast<const void*>(msm_tree_kernel<F>)};
-  for (uint32_t rmul : {1u, 3u, 5u, 7u, 9u, 11u, 13u, 15u}) ZK_DISPATCH_RMUL(rmul, fns.push_back(reinterpret_cast<const void*>(msm_digits_hist_kernel<RM>)));
-  for (const void* fn : fns) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      std::fprintf(stderr, "[mi355zk] hipFuncSetAttribute(partition kernel, 160 KiB LDS) failed: %s\n", hipGetErrorString(e));
-      rc = ZK_ERR_DEVICE;
-    }
+  int rc = zk::part_configure(dev);  // (qualified: the shared, non-template one)
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(msm_tree_kernel<F>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (e != hipSuccess) {
+    std::fprintf(stderr, "[mi355zk] hipFuncSetAttribute(partition kernel, 160 KiB LDS) failed: %s\n", hipGetErrorString(e));
+    rc = ZK_ERR_DEVICE;
   }
-  g_part_cfg[key] = rc;
+  g_part_cfg[dev] = rc;
   return rc;
 }
 
-// the call's workspace as typed pointers (MsmLayout's offsets over the leased buffer)
+// the call's workspace as typed pointers (MsmLayout's offsets over the leased buffer): the untyped part and the XYZZ records
 template <class F>
-struct MsmWs {
-  uint32_t *keys, *vals_b;  // (the index lists alias the keys: MsmLayout)
-  uint2* pairs;
-  uint16_t* tile_hist;
-  uint32_t *tile_off, *csum, *col_total, *bin_start, *out_start, *gcnt, *gcur, *big_col, *big_seg;
-  BigPlan* big_plan;
-  uint32_t *first, *last, *size_hist, *sizes_b, *order, *item_off;
+struct MsmWs : MsmPartWs {
   XYZZ<F>*seg_sums, *buckets, *partA, *partS, *rc, *wsums, *sumtmp;
-  unsigned long long* d_err;
   static_assert(sizeof(XYZZ<F>) == (sizeof(F) == sizeof(Fq) ? 128 : 256), "msm_plan.hpp sizes the record regions by these");
-  MsmWs(char* ws, const MsmLayout& L) {
-    auto at = [ws](auto*& p, size_t off) { p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(ws + off); };
-    at(keys, L.keys), at(vals_b, L.keys), at(pairs, L.pairs), at(tile_hist, L.tile_hist), at(tile_off, L.tile_off), at(csum, L.csum), at(col_total, L.total);
-    at(bin_start, L.bin_start), at(out_start, L.out_start), at(gcnt, L.gcnt), at(gcur, L.gcur), at(big_col, L.big_col), at(big_seg, L.big_seg);
-    at(big_plan, L.big_plan), at(first, L.first), at(last, L.last), at(size_hist, L.hist), at(sizes_b, L.sizes_b), at(order, L.ids_b), at(item_off, L.item_off);
-    at(seg_sums, L.seg_sums), at(buckets, L.buckets), at(partA, L.partA), at(partS, L.partS), at(rc, L.rc), at(wsums, L.wsums), at(sumtmp, L.sumtmp), at(d_err, L.err);
+  MsmWs(char* ws, const MsmLayout& L) : MsmPartWs(ws, L) {
+    at(ws, seg_sums, L.seg_sums), at(ws, buckets, L.buckets), at(ws, partA, L.partA), at(ws, partS, L.partS), at(ws, rc, L.rc), at(ws, wsums, L.wsums);
+    at(ws, sumtmp, L.sumtmp);
   }
 };
 
-// what every launch stage of one msm_device call sees
+// what every launch stage of one msm_device call sees: the group-independent context (msm_partition.hpp) and the group's own part
 template <class F>
-struct MsmCall {
-  const MsmPlan& plan;
-  const MsmKnobs& knobs;
+struct MsmCall : MsmPartCall {
   MsmWs<F> ws;
-  int dev;
-  hipStream_t st;
-  uint64_t n, base_offset, table_stride;
-  const uint32_t *d_density, *d_dprefix;  // cover the whole call
-  bool scalars_mont, dense;
+  bool dense;
 };
-
-struct MsmSlots { int digits, scan, scatter, bucket, sort, acc, heavy, red; };
-inline const MsmSlots& msm_slots() {
-  static const MsmSlots s{prof_slot("msm_digits"), prof_slot("msm_part_scan"), prof_slot("msm_scatter"), prof_slot("msm_bucket"),
-                          prof_slot("msm_sort"), prof_slot("msm_accumulate"), prof_slot("msm_accumulate_heavy"), prof_slot("msm_reduce")};
-  return s;
-}
-
-template <class F>
-int msm_checkpoint(const MsmCall<F>& A, const char* what, const ChunkPlan& C) {
-  if (!A.knobs.debug) return 0;
-  const MsmPlan& P = A.plan;
-  ZK_HIP(hipStreamSynchronize(A.st));
-  std::fprintf(stderr, "[mi355zk] msm<%d> n=%llu chunk@%llu+%llu c=%u W=%u buckets=%u levels=%u part(lo=%u nbin=%u st=%u): %s done\n",
-               (int)(sizeof(F) / sizeof(Fq)), (unsigned long long)A.n, (unsigned long long)C.lo, (unsigned long long)C.n, P.G.c, P.WL, P.n_buckets,
-               P.n_levels, C.P.lo_bits, C.P.nbin, C.P.st, what);
-  return 0;
-}
 
 // fn(A4, CARRY) with the two run-time switches of the accumulation kernels as std::bool_constants
 template <class Fn>
 void with_a4_carry(bool a4, bool carry, Fn&& fn) {
   auto with_carry = [&](auto A4) { if (carry) fn(A4, std::true_type{}); else fn(A4, std::false_type{}); };
   if (a4) with_carry(std::true_type{}); else with_carry(std::false_type{});
-}
-
-// ---- digits of one chunk: window-major keys and the tile histograms
-template <class F>
-int launch_digits(const MsmCall<F>& A, const ChunkPlan& C, const uint32_t* d_sc) {
-  const MsmPlan& P = A.plan;
-  const MsmWs<F>& W = A.ws;
-  const MsmGeom& G = P.G;
-  const PartGeom& PG = C.P;
-  const hipStream_t st = A.st;
-  const uint64_t nc = C.n, kstride = (nc + 3) & ~3ull;  // distance between the key planes of two windows
-  const uint32_t ncell = C.ncell, WL = P.WL;
-  // density words and prefix ranks of this chunk's exponents (cuts are multiples of 32); under FullDensity exponent i of the
-  // chunk owns base base_offset + lo + i
-  const uint32_t* dens = A.d_density ? A.d_density + (C.lo >> 5) : nullptr;
-  if (!C.small_scan) ZK_HIP(hipMemsetAsync(W.size_hist, 0, MSM_SIZE_BINS * 4, st));   // (msm_scan_small_kernel clears it)
-  if (C.np > BIG_SEG) ZK_HIP(hipMemsetAsync(W.gcnt, 0, P.L.big_col - P.L.gcnt, st));  // gcnt and gcur (big bins only: see the bucket pass)
-  prof_begin(msm_slots().digits, st);
-  if (!A.knobs.fused_a) {
-    ZK_DISPATCH_RMUL(G.rmul, hipLaunchKernelGGL(msm_digits_plain_kernel<RM>, dim3((unsigned)((kstride + 255) / 256)), dim3(256), 0, st, d_sc, nc, dens, G,
-                                                P.w_lo, P.w_hi, A.scalars_mont ? 1 : 0, kstride, W.keys, W.d_err + 1, C.lo));
-    hipLaunchKernelGGL(msm_tile_hist_kernel, dim3(PG.n_st * WL), dim3(PART_THREADS), (size_t)PG.nbin * 4, st, W.keys, C.np, P.tmode ? C.np : kstride, G.nb, WL, PG,
-                       W.tile_hist);
-  } else {
-    if (P.tmode) return (int)ZK_ERR_BAD_ARGS;
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, A.dev);
-    const uint32_t per_cu = (size_t)((ncell + 1) / 2) * 4 <= PART_LDS_A ? 2u : 1u;     // 1024-lane workgroups per CU (LDS histograms)
-    const uint32_t grid = PG.n_st < per_cu * (uint32_t)cus ? PG.n_st : per_cu * (uint32_t)cus;
-    ZK_DISPATCH_RMUL(G.rmul, hipLaunchKernelGGL(msm_digits_hist_kernel<RM>, dim3(grid), dim3(PART_THREADS), (size_t)((ncell + 1) / 2) * 4, st, d_sc, nc,
-                                                dens, G, P.w_lo, P.w_hi, A.scalars_mont ? 1 : 0, PG, kstride, W.keys, W.tile_hist, W.d_err + 1, C.lo));
-  }
-  ZK_HIP(hipGetLastError());
-  prof_end(msm_slots().digits, st);
-  if (msm_checkpoint(A, "digits", C)) return ZK_ERR_DEVICE;
-  return ZK_OK;
-}
-
-// ---- partition of one chunk: index lists per (window, bucket) in vals_b, bounds first[] / last[], size order
-// ("msm_sort" spans the whole partition after the digits (scan + scatter + bucket + size order), as it did for the library sort)
-template <class F>
-int launch_partition(const MsmCall<F>& A, const ChunkPlan& C) {
-  const MsmPlan& P = A.plan;
-  const MsmWs<F>& W = A.ws;
-  const MsmGeom& G = P.G;
-  const PartGeom& PG = C.P;
-  const MsmSlots& S = msm_slots();
-  const hipStream_t st = A.st;
-  const uint64_t nc = C.n, kstride = (nc + 3) & ~3ull;
-  const uint32_t ncell = C.ncell, WL = P.WL;
-  const uint32_t* dens = A.d_density ? A.d_density + (C.lo >> 5) : nullptr;
-  const uint32_t* dpre = A.d_dprefix ? A.d_dprefix + (C.lo >> 5) : nullptr;
-  const uint64_t boff = A.base_offset + (A.d_density ? 0 : C.lo);
-  prof_begin(S.sort, st);
-  prof_begin(S.scan, st);
-  if (C.small_scan) {
-    hipLaunchKernelGGL(msm_scan_small_kernel, dim3(1), dim3(PART_THREADS), 0, st, W.tile_hist, PG, ncell, G.nb, W.col_total, W.bin_start, W.out_start, W.tile_off,
-                       W.size_hist, W.big_col, W.big_seg, W.big_plan);
-  } else {
-    hipLaunchKernelGGL(msm_colsum_kernel, dim3((ncell + 255) / 256, PG.n_chunk), dim3(256), 0, st, W.tile_hist, PG, ncell, W.csum);
-    hipLaunchKernelGGL(msm_colscan_kernel, dim3((ncell + 255) / 256), dim3(256), 0, st, W.csum, PG, ncell, W.col_total);
-    hipLaunchKernelGGL(msm_binscan_kernel, dim3(1), dim3(PART_THREADS), 0, st, W.col_total, PG, ncell, G.nb, W.bin_start, W.out_start);
-    hipLaunchKernelGGL(msm_tileoff_kernel, dim3((ncell + 255) / 256, PG.n_chunk), dim3(256), 0, st, W.tile_hist, W.csum, W.bin_start, PG, ncell, W.tile_off);
-  }
-  ZK_HIP(hipGetLastError());
-  prof_end(S.scan, st);
-  prof_begin(S.scatter, st);
-  hipLaunchKernelGGL(msm_scatter_kernel, dim3(PG.n_st * WL), dim3(PART_THREADS), (size_t)(2 * ((PG.nbin + 3u) & ~3u) + 32) * 4 + (size_t)PG.st * 8, st,
-                     W.keys, C.np, P.tmode ? C.np : kstride, boff, dens, dpre, G.nb, WL, PG, A.knobs.part_xcds, W.tile_off, W.pairs, P.tmode ? kstride : 0ull,
-                     A.table_stride);
-  ZK_HIP(hipGetLastError());
-  prof_end(S.scatter, st);
-  if (msm_checkpoint(A, "scatter", C)) return ZK_ERR_DEVICE;
-  prof_begin(S.bucket, st);
-  {
-    const uint32_t nfl = (1u << PG.lo_bits) < 4 ? 4 : (1u << PG.lo_bits);
-    const size_t fixed = (size_t)(2 * nfl + 32) * 4;
-    // staging for the expected bin population with slack, at most what the CU has
-    uint64_t want = (uint64_t)(C.np / PG.nbin) * 5 / 4 + 3ull * nfl + 4096;
-    const uint64_t cap_max = (PART_LDS_MAX - fixed) / 4;
-    if (want > cap_max) want = cap_max;
-    if (want > (uint64_t)PART_EC * PART_THREADS + 3ull * nfl) want = (uint64_t)PART_EC * PART_THREADS + 3ull * nfl;
-    const uint32_t stage_cap = (uint32_t)want & ~3u;
-    hipLaunchKernelGGL(msm_bucket_kernel, dim3(ncell), dim3(PART_THREADS), fixed + (size_t)stage_cap * 4, st, W.pairs, W.bin_start, W.out_start, G.nb, PG,
-                       stage_cap, W.first, W.last, W.vals_b);
-    // the big bins (none for uniform exponents up to 2^26 points: the surplus workgroups of these launches exit at once).  A
-    // chunk with at most BIG_SEG elements per window cannot have one at all -- the bucket kernel took every bin -- so a short call
-    // does not pay for three idle launches (~5 us each of a 0.4-ms call at 2^10 .. 2^15 points)
-    if (C.np > BIG_SEG) {
-      const uint32_t max_seg = (uint32_t)(2 * (C.m / BIG_SEG) + 2);
-      if (!C.small_scan) hipLaunchKernelGGL(msm_bigbin_plan_kernel, dim3(1), dim3(PART_THREADS), 0, st, W.bin_start, ncell, W.big_col, W.big_seg, W.big_plan);
-      // (small grids: when there is no big bin -- uniform exponents -- the launches only cost their workgroups' start-up, and the
-      // place kernel's LDS allows one workgroup per CU anyway)
-      int n_cu = 256;
-      (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, A.dev);
-      const uint32_t big_grid = max_seg < 2u * (uint32_t)n_cu ? max_seg : 2u * (uint32_t)n_cu;
-      const uint32_t place_grid = max_seg < (uint32_t)n_cu ? max_seg : (uint32_t)n_cu;
-      hipLaunchKernelGGL(msm_bigbin_count_kernel, dim3(big_grid), dim3(PART_THREADS), (size_t)nfl * 4, st, W.pairs, W.bin_start, W.big_plan, W.big_col, W.big_seg,
-                         G.nb, PG, W.gcnt);
-      const size_t place_fixed = (size_t)(4 * nfl + 32) * 4, place_staged = place_fixed + (size_t)BIG_SEG * 4;
-      const int staged = place_staged <= PART_LDS_MAX ? 1 : 0;
-      hipLaunchKernelGGL(msm_bigbin_place_kernel, dim3(staged ? place_grid : big_grid), dim3(PART_THREADS), staged ? place_staged : place_fixed, st, W.pairs,
-                         W.bin_start, W.out_start, W.big_plan, W.big_col, W.big_seg, G.nb, PG, staged, W.gcnt, W.gcur, W.first, W.last, W.vals_b);
-    }
-  }
-  ZK_HIP(hipGetLastError());
-  prof_end(S.bucket, st);
-  if (msm_checkpoint(A, "bucket", C)) return ZK_ERR_DEVICE;
-  msm_order_by_size(W.first, W.last, P.n_buckets, W.size_hist, W.order, W.sizes_b, st);
-  ZK_HIP(hipGetLastError());
-  prof_end(S.sort, st);
-  if (msm_checkpoint(A, "partition", C)) return ZK_ERR_DEVICE;
-  return ZK_OK;
 }
 
 // ---- the segment-parallel path for the buckets longer than `heavy` among order[0 .. hb): plan, segment sums, sums per bucket
@@ -238,7 +73,7 @@ struct HeavyParams {
 template <class F>
 int launch_heavy(hipStream_t st, const Affine<F>* bases, const uint32_t* vals, const uint32_t* first, const uint32_t* last, const uint32_t* order,
                  const uint32_t* sizes_b, uint32_t* item_off, XYZZ<F>* seg_sums, XYZZ<F>* buckets, unsigned long long* d_err, const HeavyParams& H) {
-  hipLaunchKernelGGL(msm_heavy_plan_kernel, dim3(1), dim3(1024), 0, st, sizes_b, H.hb, H.heavy, H.seg, item_off);
+  launch_heavy_plan(st, sizes_b, H.hb, H.heavy, H.seg, item_off);
   ZK_HIP(hipGetLastError());
   hipLaunchKernelGGL(msm_accumulate_heavy_kernel<F>, dim3(H.grid), dim3(MSM_HEAVY_LANES), MSM_HEAVY_LANES * sizeof(typename BucketAcc<F>::type), st, bases, vals,
                      first, last, order, item_off, H.hb, H.seg, seg_sums, H.dense, d_err);
@@ -545,7 +380,7 @@ int msm_device(const Affine<F>* d_bases, uint64_t n_bases, uint64_t base_offset,
     rc = ws_reserve(dev_ws, P.L.total_bytes, &base);
   }
   if (rc) return rc;
-  const MsmCall<F> A{P, K, MsmWs<F>((char*)base, P.L), dev, st, n, base_offset, table_stride, d_density, d_dprefix, scalars_mont, dense};
+  const MsmCall<F> A{{P, K, R.group, dev, st, n, base_offset, table_stride, d_density, d_dprefix, scalars_mont}, MsmWs<F>((char*)base, P.L), dense};
   ZK_HIP(hipMemsetAsync(A.ws.d_err, 0xff, 16, st));
   lease.idle = false;
 
@@ -560,9 +395,9 @@ int msm_device(const Affine<F>* d_bases, uint64_t n_bases, uint64_t base_offset,
       d_sc = (const uint32_t*)p;
     }
     d_sc_first = d_sc;  // (table mode runs a single chunk: its exponents, for the error path's rescan)
-    rc = launch_digits(A, C, d_sc);
+    rc = launch_digits(A, A.ws, C, d_sc);
     if (rc == ZK_OK && chunks) rc = chunks->digits_enqueued(c, st);  // the digit kernel is the only reader of the exponents
-    if (rc == ZK_OK) rc = launch_partition(A, C);
+    if (rc == ZK_OK) rc = launch_partition(A, A.ws, C);
     if (rc == ZK_OK) rc = launch_accumulate(A, C, d_bases, c > 0);
     if (rc) return rc;
   }
@@ -614,7 +449,7 @@ int segsum_device(const Affine<F>* d_points, uint64_t nnz, const uint32_t* d_row
   uint32_t* item_off = (uint32_t*)(ws + o_item_off);
   XYZZ<F>* seg_sums = (XYZZ<F>*)(ws + o_seg);
   XYZZ<F>* buckets = (XYZZ<F>*)(ws + o_buckets);
-  if (nnz) hipLaunchKernelGGL(msm_iota_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, vals, (uint32_t)nnz);
+  if (nnz) launch_iota(st, vals, (uint32_t)nnz);
   ZK_HIP(hipMemsetAsync(size_hist, 0, MSM_SIZE_BINS * 4, st));
   msm_order_by_size(first, last, n_rows, size_hist, order, sizes_b, st);
   ZK_HIP(hipGetLastError());

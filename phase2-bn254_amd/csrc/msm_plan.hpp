@@ -13,8 +13,6 @@
 
 namespace zk {
 
-namespace {
-
 // Every environment knob of the multiexp's host side, read in ONE place (msm_knobs); the planner, the launch stages and the join take
 // them as an argument.  Experiment / comparison switches unless noted; the defaults below are what an empty environment gives.
 struct MsmKnobs {
@@ -498,7 +496,5 @@ inline MsmPlan msm_plan(const MsmRequest& R, const MsmKnobs& K) {
   P.rc = msm_plan_fill(R, K, P);
   return P;
 }
-
-}  // namespace
 
 }  // namespace zk

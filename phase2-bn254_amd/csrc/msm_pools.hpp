@@ -1,6 +1,7 @@
 #pragma once
-// Device workspaces and pinned host buffers of the multiexp (msm_host.hpp).  One set per translation unit: G1 and G2 calls do not share
-// a device workspace or its mutex.
+// Device workspaces and pinned host buffers of the multiexp (msm_host.hpp).  Per unit ON PURPOSE (an anonymous namespace, unlike
+// msm_common.hpp / msm_plan.hpp / msm_partition.hpp, which msm_g1.hip and msm_g2.hip share): G1 and G2 calls keep separate device
+// workspaces, mutexes and pin pools, so a G1 and a G2 multiexp on one device never wait for each other's workspace.
 #include <hip/hip_runtime.h>
 
 #include <map>

@@ -1,4 +1,4 @@
-"""The signed-digit extraction of the multiexp (msm_impl.hpp: power-of-two and mixed-radix windows) on the HOST, through the
+"""The signed-digit extraction of the multiexp (msm_digits.hpp: power-of-two and mixed-radix windows) on the HOST, through the
 library's self-test hook: (1) the digits reconstruct the scalar, sum_w d_w * weight_w == k, with every digit in its signed
 range; (2) a window-group rank's digits -- chain started one window below its first window, fallback on the sign boundary --
 equal the plain chain's for every group start, on random scalars and on scalars crafted to sit ON the boundary (raw digit of

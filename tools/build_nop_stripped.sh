@@ -14,7 +14,7 @@ OUT=build/nonop
 mkdir -p $OUT
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude -Wno-unused-result"
 OBJS=""
-for tu in ntt msm_g1 msm_g2 api field_ops point_fft point_fft_g2 codec; do
+for tu in ntt msm_g1 msm_g2 msm_partition api field_ops point_fft point_fft_g2 codec; do
   if [[ " $* " == *" $tu "* ]]; then
     hipcc $FLAGS --cuda-device-only -S phase2-bn254_amd/csrc/$tu.hip -o $OUT/$tu.s 2>/dev/null
     python3 - $OUT/$tu.s $OUT/${tu}_stripped.s <<'PY'
