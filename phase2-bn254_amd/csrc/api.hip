@@ -1,29 +1,22 @@
 // C ABI of libmi355zk.so (include/mi355zk.h): the extern "C" entry points (argument checking, abi_guard), the domain constants of
-// bellman/src/domain.rs:52-99, lifecycle, and the kernel-timing hooks used by bench.py.  The machinery behind the host-buffer entry points
-// (Source / Density plan, bases cache, streamed upload, multi-GPU cells) is host_entry.hip, the scalar-multiplication kernels scalar_mul.hip;
-// api_internal.hpp is the interface between the three.
+// bellman/src/domain.rs:52-99, lifecycle, and the kernel-timing hooks used by bench.py.  The machinery behind the host-buffer entry points is
+// host_entry.hip (the multiexp: streamed upload, multi-GPU cells), host_ops.hip (batch_exp, dense multiexp, NTT, H polynomial, sparse matvec),
+// bases_cache.hip and host_pools.hip; the scalar-multiplication kernels are scalar_mul.hip; api_internal.hpp is the interface between the units.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
+#include <cstdio>
 #include <cstring>
-#include <exception>
 #include <map>
-#include <memory>
 #include <mutex>
-#include <thread>
-#include <utility>
 #include <string>
-#include <type_traits>
-#include <algorithm>
 #include <vector>
 
 #include "../../include/mi355zk.h"
 #include "curveu.hpp"
-#include "glv.hpp"
 #include "device_util.hpp"
 #include "api_internal.hpp"
+#include "bases_cache.hpp"
+#include "host_pools.hpp"
 
 namespace zk {
 

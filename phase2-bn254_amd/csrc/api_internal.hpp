@@ -1,6 +1,10 @@
 // Internal interfaces between the translation units of libmi355zk.so (not part of the C ABI: include/mi355zk.h is).
 //   api.hip         the C ABI: argument checking, domain constants, device-resident entry points, profiling hooks, lifecycle
-//   host_entry.hip  the host-buffer entry points: Source / Density plan, bases cache, streamed upload, multi-GPU cells
+//   host_entry.hip  the multiexp behind the ABI: device-resident call wrapper, streamed upload of a host-buffer call, multi-GPU cells
+//   host_ops.hip    the other host-buffer entry points: batch_exp, dense multiexp / merge_pairs, NTT, H polynomial, QAP sparse matvec
+//   host_plan.hpp   what those two plan, without a device: Source / Density arithmetic, chunk schedule, cells and their join, row cuts, knobs
+//   bases_cache.hip the pinned-bases cache (bases_cache.hpp: its interface; the entries and their lock are its own)
+//   host_pools.hip  the stage pool and the device set (host_pools.hpp: leases, events, the fan-out over devices)
 //   scalar_mul.hip  the scalar-multiplication kernels and their launchers: batch_exp / batch_mul / window-table build / G2 membership
 //   fr_random.hip   the random exponents of merge_pairs generated on the device (chacha.hpp: the generator shared with the host)
 //   accumulator_stream.hip  powers-of-tau files streamed through the device: wire records in host memory on both sides, bounded pieces
@@ -115,11 +119,6 @@ int domain_op_batch_dev(Fr* const* d_arrays, uint32_t batch, uint32_t log_n, int
 int h_poly_finish_dev(Fr* d_a, const Fr* d_b, const Fr* d_c, uint32_t log_n, uint32_t flags, hipStream_t st);
 
 // host_entry.hip
-struct DeviceGuard {  // the calling thread's current device is its own business: restore it
-  int prev = -1;
-  DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
-  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 extern thread_local long long t_last_err_index;   // exponent index of the last Source error of this thread's calls (mi355zk_last_error_index)
 // the device-resident multiexp behind every _dev entry point (table: d_bases is a window table; chunks: exponents handed over while the call runs)
 template <int GROUP>
@@ -130,12 +129,32 @@ int msm_dev_entry(const void* d_bases, size_t n_bases, size_t base_offset, const
 template <int GROUP>
 int msm_host_entry(const uint8_t* bases, size_t n_bases, size_t base_offset, const uint64_t* scalars, size_t n_scalars, const uint32_t* density,
                    size_t density_bits, uint64_t* out_xyz, const RecordLayout& L = RecordLayout());
+extern template int msm_dev_entry<1>(const void*, size_t, size_t, const void*, size_t, const uint32_t*, size_t, void*, uint64_t*, uint32_t, uint32_t, uint32_t, MsmChunks*, bool);
+extern template int msm_dev_entry<2>(const void*, size_t, size_t, const void*, size_t, const uint32_t*, size_t, void*, uint64_t*, uint32_t, uint32_t, uint32_t, MsmChunks*, bool);
+extern template int msm_host_entry<1>(const uint8_t*, size_t, size_t, const uint64_t*, size_t, const uint32_t*, size_t, uint64_t*, const RecordLayout&);
+extern template int msm_host_entry<2>(const uint8_t*, size_t, size_t, const uint64_t*, size_t, const uint32_t*, size_t, uint64_t*, const RecordLayout&);
+// host_ops.hip
 template <class F>
 int batch_exp_host(uint8_t* out, const uint8_t* bases, const uint64_t* scalars, size_t n, int same_scalar, bool g2_trusted);
 // rnd != nullptr: rho is not read -- every piece fills its exponents on its device from the scalar stream of chacha.hpp, from the piece's first index
 template <int GROUP>
 int dense_host(const uint8_t* v1, const uint8_t* v2, const uint64_t* rho, size_t n, uint64_t* out_s, uint64_t* out_sx, const FrRandomStream* rnd = nullptr);
 int ntt_host(uint64_t* a, uint32_t log_n, int op, const uint64_t* omega);
+int h_poly_host(uint64_t* h, const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t len, uint32_t log_n, uint32_t flags);
+template <class F>
+int sparse_matvec(void* d_out, const void* d_bases, size_t n_bases, const uint32_t* d_row_ptr, const uint32_t* d_col, const void* d_coeffs,
+                  size_t n_rows, size_t nnz, void* stream, int group, bool g2_trusted, void* d_scratch = nullptr, size_t scratch_bytes = 0);
+template <class F>
+int sparse_matvec_host(uint8_t* out, const uint8_t* bases, size_t n_bases, const uint32_t* row_ptr, const uint32_t* col, const uint64_t* coeffs,
+                       size_t n_rows, size_t nnz, int group, bool g2_trusted);
+extern template int batch_exp_host<Fq>(uint8_t*, const uint8_t*, const uint64_t*, size_t, int, bool);
+extern template int batch_exp_host<Fq2>(uint8_t*, const uint8_t*, const uint64_t*, size_t, int, bool);
+extern template int dense_host<1>(const uint8_t*, const uint8_t*, const uint64_t*, size_t, uint64_t*, uint64_t*, const FrRandomStream*);
+extern template int dense_host<2>(const uint8_t*, const uint8_t*, const uint64_t*, size_t, uint64_t*, uint64_t*, const FrRandomStream*);
+extern template int sparse_matvec<Fq>(void*, const void*, size_t, const uint32_t*, const uint32_t*, const void*, size_t, size_t, void*, int, bool, void*, size_t);
+extern template int sparse_matvec<Fq2>(void*, const void*, size_t, const uint32_t*, const uint32_t*, const void*, size_t, size_t, void*, int, bool, void*, size_t);
+extern template int sparse_matvec_host<Fq>(uint8_t*, const uint8_t*, size_t, const uint32_t*, const uint32_t*, const uint64_t*, size_t, size_t, int, bool);
+extern template int sparse_matvec_host<Fq2>(uint8_t*, const uint8_t*, size_t, const uint32_t*, const uint32_t*, const uint64_t*, size_t, size_t, int, bool);
 // accumulator_stream.hip (include/mi355zk.h: mi355zk_bn254_g{1,2}_accumulator_transform / _power_pairs)
 template <int GROUP>
 int accumulator_transform(uint8_t* out, const uint8_t* in, size_t n, uint64_t first, const uint64_t* tau, const uint64_t* coeff, int in_compressed,
@@ -147,30 +166,4 @@ extern template int accumulator_transform<1>(uint8_t*, const uint8_t*, size_t, u
 extern template int accumulator_transform<2>(uint8_t*, const uint8_t*, size_t, uint64_t, const uint64_t*, const uint64_t*, int, int, int, uint32_t, size_t, long long*);
 extern template int accumulator_power_pairs<1>(const uint8_t*, size_t, int, int, int, const uint32_t*, uint64_t, uint64_t, uint8_t*, size_t, uint64_t*, uint64_t*, long long*);
 extern template int accumulator_power_pairs<2>(const uint8_t*, size_t, int, int, int, const uint32_t*, uint64_t, uint64_t, uint8_t*, size_t, uint64_t*, uint64_t*, long long*);
-int h_poly_host(uint64_t* h, const uint64_t* a, const uint64_t* b, const uint64_t* c, size_t len, uint32_t log_n, uint32_t flags);
-template <class F>
-int sparse_matvec(void* d_out, const void* d_bases, size_t n_bases, const uint32_t* d_row_ptr, const uint32_t* d_col, const void* d_coeffs,
-                  size_t n_rows, size_t nnz, void* stream, int group, bool g2_trusted, void* d_scratch = nullptr, size_t scratch_bytes = 0);
-template <class F>
-int sparse_matvec_host(uint8_t* out, const uint8_t* bases, size_t n_bases, const uint32_t* row_ptr, const uint32_t* col, const uint64_t* coeffs,
-                       size_t n_rows, size_t nnz, int group, bool g2_trusted);
-extern template int msm_dev_entry<1>(const void*, size_t, size_t, const void*, size_t, const uint32_t*, size_t, void*, uint64_t*, uint32_t, uint32_t, uint32_t, MsmChunks*, bool);
-extern template int msm_dev_entry<2>(const void*, size_t, size_t, const void*, size_t, const uint32_t*, size_t, void*, uint64_t*, uint32_t, uint32_t, uint32_t, MsmChunks*, bool);
-extern template int msm_host_entry<1>(const uint8_t*, size_t, size_t, const uint64_t*, size_t, const uint32_t*, size_t, uint64_t*, const RecordLayout&);
-extern template int msm_host_entry<2>(const uint8_t*, size_t, size_t, const uint64_t*, size_t, const uint32_t*, size_t, uint64_t*, const RecordLayout&);
-extern template int batch_exp_host<Fq>(uint8_t*, const uint8_t*, const uint64_t*, size_t, int, bool);
-extern template int batch_exp_host<Fq2>(uint8_t*, const uint8_t*, const uint64_t*, size_t, int, bool);
-extern template int dense_host<1>(const uint8_t*, const uint8_t*, const uint64_t*, size_t, uint64_t*, uint64_t*, const FrRandomStream*);
-extern template int dense_host<2>(const uint8_t*, const uint8_t*, const uint64_t*, size_t, uint64_t*, uint64_t*, const FrRandomStream*);
-extern template int sparse_matvec<Fq>(void*, const void*, size_t, const uint32_t*, const uint32_t*, const void*, size_t, size_t, void*, int, bool, void*, size_t);
-extern template int sparse_matvec<Fq2>(void*, const void*, size_t, const uint32_t*, const uint32_t*, const void*, size_t, size_t, void*, int, bool, void*, size_t);
-extern template int sparse_matvec_host<Fq>(uint8_t*, const uint8_t*, size_t, const uint32_t*, const uint32_t*, const uint64_t*, size_t, size_t, int, bool);
-extern template int sparse_matvec_host<Fq2>(uint8_t*, const uint8_t*, size_t, const uint32_t*, const uint32_t*, const uint64_t*, size_t, size_t, int, bool);
-// the caller's promise of immutability (include/mi355zk.h); lay: the records' layout (part of the pin and of the cache key)
-int bases_cache_pin(const void* host, size_t n, int group, bool tables = false, const RecordLayout& lay = RecordLayout());
-void bases_cache_invalidate(const void* host);
-int bases_cache_info(const void* host_bases, size_t* device_bytes, size_t* table_bytes);
-void devset_set(const std::vector<int>& set);   // the device set of mi355zk_init (empty: the current device)
-int devset_count();
-void host_entry_release_all();
 }  // namespace zk

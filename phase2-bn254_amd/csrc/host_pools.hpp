@@ -1,15 +1,32 @@
 // What a host-buffer entry point holds while it runs: grow-only device buffers leased from a pool, a stage (a copy and a compute stream) and
-// the call's events.  Shared by host_entry.hip (which owns the stage pool) and accumulator_stream.hip.
+// the call's events; the device set of mi355zk_init and the fan-out of a call over it.  Shared by host_entry.hip, host_ops.hip and
+// accumulator_stream.hip; the stage pool and the device set themselves are host_pools.hip's.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstddef>
+#include <cstdlib>
+#include <exception>
 #include <mutex>
+#include <thread>
 #include <vector>
 
 #include "device_util.hpp"
 
 namespace zk {
+struct DeviceGuard {  // the calling thread's current device is its own business: restore it
+  int prev = -1;
+  DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
+  ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+inline bool trace_host() {  // MI355ZK_TRACE_HOST: timeline of the streamed / multi-device call on stderr
+  static const bool on = std::getenv("MI355ZK_TRACE_HOST") != nullptr;
+  return on;
+}
+inline double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+
 // a grow-only device allocation.  reserve() regrows by free + malloc: the owner knows that nothing queued still uses the old one
 struct DevBuf {
   void* p = nullptr;
@@ -82,7 +99,7 @@ struct HostStage {
   DevBuf raw;     // strided records: one bounded piece of the caller's raw records on its way to records_pack
   hipStream_t copy = nullptr, compute = nullptr;
 };
-extern std::mutex g_stage_mu;      // host_entry.hip: the pool of stages
+extern std::mutex g_stage_mu;      // host_pools.hip: the pool of stages
 HostStage* host_stage(int dev);    // an idle stage of the device, marked busy (nullptr: no streams to be had)
 
 // What a host-buffer call holds while it runs: a stage (its two streams) and, with bytes > 0, one buffer of the pool.  On every exit
@@ -127,4 +144,45 @@ struct Events {
   }
   hipEvent_t operator[](size_t i) const { return e[i]; }
 };
+
+// The device set of mi355zk_init (host_pools.hip): HIP device ids; a test may repeat one id (logical devices sharing a GPU).
+void devset_set(const std::vector<int>& set);   // (empty: the current device)
+int devset_count();
+std::vector<int> devset_snapshot();
+int devset_or_current(std::vector<int>* devs);  // the device set, or the calling thread's current device when none was given
+unsigned devset_turn();                         // a counter that deals short calls out to the devices of the set in turn
+void host_entry_release_all();                  // the device memory of the bases cache, the stages and the buffer pool (mi355zk_shutdown)
+
+// The fan-out of a call over its cells / ranges / workers: fn(0) .. fn(count - 1), unit 0 on the calling thread, every other unit on a host
+// thread of its own; the units whose thread could not be had run here afterwards, one after the other.  Returns the units' return codes.
+// Nothing is thrown out of a host thread or across the C ABI (std::bad_alloc from a staging vector, a std::system_error from a lock): the
+// unit fails as a device error.  The calling thread's current device is restored.
+template <class Fn>
+std::vector<int> fan_out(size_t count, Fn&& fn) {
+  std::vector<int> rcs(count, ZK_OK);
+  auto unit = [&](size_t i) noexcept {
+    try {
+      rcs[i] = fn(i);
+    } catch (...) {
+      rcs[i] = ZK_ERR_DEVICE;
+    }
+  };
+  DeviceGuard guard;
+  std::vector<std::thread> th;
+  size_t started = 1;
+  try {
+    for (; started < count; ++started) th.emplace_back([&, started] { unit(started); });
+  } catch (const std::exception&) {
+    // (no more host threads to be had -- nothing is thrown across the C ABI)
+  }
+  if (count) unit(0);
+  for (size_t i = started; i < count; ++i) unit(i);
+  for (auto& t : th) t.join();
+  return rcs;
+}
+inline int first_error(const std::vector<int>& rcs) {
+  for (int rc : rcs)
+    if (rc != ZK_OK) return rc;
+  return ZK_OK;
+}
 }  // namespace zk

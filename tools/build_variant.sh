@@ -8,7 +8,7 @@ name=$1; flags=$2; shift 2 || true
 units=${@:-msm_g1}
 mkdir -p build_$name tools/bin
 objs=""; pids=""
-for o in ntt msm_g1 msm_g2 msm_partition api host_entry scalar_mul fixed_base field_ops r1cs point_fft point_fft_g2 codec records selftest_dev selftest_dev_chain; do
+for o in ntt msm_g1 msm_g2 msm_partition api host_entry host_ops bases_cache host_pools accumulator_stream scalar_mul fixed_base pairing fr_random field_ops r1cs point_fft point_fft_g2 codec records selftest_dev selftest_dev_chain; do
   if [[ " $units " == *" $o "* ]]; then
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude -Wno-unused-result $flags -c phase2-bn254_amd/csrc/$o.hip -o build_$name/$o.o &
     pids="$pids $!"
