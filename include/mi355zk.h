@@ -395,6 +395,10 @@ int mi355zk_selftest_g2_accumulate(int mode, const uint64_t *affine_pts, const u
  * scalar multiplication (group: 1 = G1, 8 + 8 u64; 2 = G2, 16 + 16 u64; 3 = a base the table build would refuse) */
 int mi355zk_selftest_fixed_base_digits(const uint64_t k[4], int16_t digits[32]);
 int mi355zk_selftest_fixed_base_mul(int group, const uint64_t *base_affine, const uint64_t k[4], uint64_t *out_affine);
+/* one row of mi355zk_bn254_g1_fixed_bases_lincomb_dev on the host, the program of its one-slice lane: first + sum_j scalars[j] * bases[j]
+ * (bases n_bases x 8 u64, scalars n_bases x 4 u64 canonical; first_affine may be NULL = the identity).  3 = a NULL pointer, a base off the curve */
+int mi355zk_selftest_fixed_bases_lincomb(const uint64_t *bases_affine, size_t n_bases, const uint64_t *first_affine, const uint64_t *scalars,
+                                         uint64_t out_affine[8]);
 
 /* ---- self-test hook ON THE DEVICE: one primitive of csrc/field.hpp / fieldu.hpp / curveu.hpp per lane, on operands the caller chose, so
  * that the gfx950 object code -- and the code that exists in the device pass only: the Montgomery product of mont_mul_gfx950.inc, the quad-
@@ -520,6 +524,31 @@ int mi355zk_bn254_g1_fixed_base_build_dev(void *d_table, size_t table_bytes, con
 int mi355zk_bn254_g2_fixed_base_build_dev(void *d_table, size_t table_bytes, const uint64_t base_affine[16], void *stream);
 int mi355zk_bn254_g1_fixed_base_mul_dev(void *d_out_affine, const void *d_table, const void *d_scalars, size_t n, uint32_t flags, void *stream);
 int mi355zk_bn254_g2_fixed_base_mul_dev(void *d_out_affine, const void *d_table, const void *d_scalars, size_t n, uint32_t flags, void *stream);
+/* ---- linear combinations over a SET of fixed G1 bases: out[i] = first + sum_{j < n_bases} k[i][j] * P_j, i < n, affine (all-zero =
+ * infinity).  The input accumulators ic[0] + sum_j x_j ic[j + 1] of groth16/verifier.rs:44-48 for n proofs against one verifying key are one
+ * call, one lane per proof; so is a single combination over many bases (n = 1), cut into slices of bases over many lanes.
+ * A table set is n_bases tables of the geometry above laid end to end (table j starts at entry j * 4096): mi355zk_fixed_bases_table_bytes(n_bases)
+ * bytes, 0 when that count cannot be served (n_bases * 4096 >= 2^31).
+ * build: bases_affine = n_bases x 8 u64 in HOST memory.  One-time work, SYNCHRONISES `stream`; one batch_exp over all n_bases * 4096 entries.
+ *   The all-zero record (the identity) is a base like any other: its table is all zero and contributes nothing.  n_bases == 0 succeeds and
+ *   touches nothing.  3 (before any device work) = a NULL pointer, table_bytes too small, a base off the curve.
+ * lincomb: d_scalars = n x n_bases canonical FrRepr, row-major (a scalar >= r: that row is unspecified, as above); d_first_affine = ONE
+ *   device record, or NULL for the identity.  A lane serves one (row, slice of slice_len consecutive bases) and runs the fixed-base program
+ *   once per base into one accumulator, through the general additions: a partial sum that equals the entry added, its negative, or the
+ *   identity is handled.  With one slice the lane adds `first` itself; with several, the slices' sums go through stream-ordered scratch
+ *   and a second kernel adds them per row.  slice_len == 0: the plan below; any other value is taken as given (clamped to n_bases).
+ *   Asynchronous on `stream`, at most 2^18 lanes per launch; n == 0 succeeds and launches nothing; n_bases == 0 gives `first` n times.
+ *   3 = a NULL pointer with work to do, n >= 2^31, n times the slice count >= 2^31.
+ * plan: host arithmetic.  slice_len >= 1 and n_slices = ceil(n_bases / slice_len) (0 for n_bases == 0): no more slices than bring n * n_slices
+ *   to MI355ZK_FIXED_BASES_LANE_TARGET lanes (ONE slice whenever n alone reaches the target), and no slice shorter than
+ *   sqrt(n_bases / 16) bases, where a lane's walk over its slice and the join's walk over the slices take equally long.
+ *   3 = a NULL pointer, n >= 2^31.  Both figures are measured: profiles/verify_proofs.md. */
+#define MI355ZK_FIXED_BASES_LANE_TARGET 262144u
+size_t mi355zk_fixed_bases_table_bytes(size_t n_bases);
+int mi355zk_fixed_bases_plan(size_t n, size_t n_bases, size_t *slice_len, size_t *n_slices);
+int mi355zk_bn254_g1_fixed_bases_build_dev(void *d_tables, size_t table_bytes, const uint64_t *bases_affine, size_t n_bases, void *stream);
+int mi355zk_bn254_g1_fixed_bases_lincomb_dev(void *d_out_affine, const void *d_tables, size_t n_bases, const void *d_first_affine,
+                                             const void *d_scalars, size_t n, size_t slice_len, void *stream);
 /* ---- per-point batch exponentiation out[i] = k[i] * P[i] (powersoftau `batch_exp`, batched_accumulator.rs:1130-1181) or, with
  * MI355ZK_EXP_SAME_SCALAR in `mode`, out[i] = k[0] * P[i] (phase2 contribute, phase2/src/parameters.rs:423-470), normalised to affine
  * like `batch_normalization` (ec.rs:251-299); the all-zero record is infinity on both sides.  mode: MI355ZK_EXP_SAME_SCALAR |

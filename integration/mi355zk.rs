@@ -129,6 +129,10 @@ extern "C" {
     pub fn mi355zk_bn254_g2_fixed_base_build_dev(d_table: *mut c_void, table_bytes: usize, base_affine: *const u64 /* [16] */, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_g1_fixed_base_mul_dev(d_out_affine: *mut c_void, d_table: *const c_void, d_scalars: *const c_void, n: usize, flags: u32, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_g2_fixed_base_mul_dev(d_out_affine: *mut c_void, d_table: *const c_void, d_scalars: *const c_void, n: usize, flags: u32, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_fixed_bases_table_bytes(n_bases: usize) -> usize;
+    pub fn mi355zk_fixed_bases_plan(n: usize, n_bases: usize, slice_len: *mut usize, n_slices: *mut usize) -> c_int;
+    pub fn mi355zk_bn254_g1_fixed_bases_build_dev(d_tables: *mut c_void, table_bytes: usize, bases_affine: *const u64, n_bases: usize, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_bn254_g1_fixed_bases_lincomb_dev(d_out_affine: *mut c_void, d_tables: *const c_void, n_bases: usize, d_first_affine: *const c_void, d_scalars: *const c_void, n: usize, slice_len: usize, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_g1_batch_exp_dev(d_out_affine: *mut c_void, d_bases_affine: *const c_void, d_scalars: *const c_void, n: usize, mode: c_int, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_g2_batch_exp_dev(d_out_affine: *mut c_void, d_bases_affine: *const c_void, d_scalars: *const c_void, n: usize, mode: c_int, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_g1_batch_exp(out_affine: *mut u8, bases_affine: *const u8, scalars: *const u64, n: usize, mode: c_int) -> c_int;

@@ -8,7 +8,8 @@
 //   scalar_mul.hip  the scalar-multiplication kernels and their launchers: batch_exp / batch_mul / window-table build / G2 membership
 //   fr_random.hip   the random exponents of merge_pairs generated on the device (chacha.hpp: the generator shared with the host)
 //   accumulator_stream.hip  powers-of-tau files streamed through the device: wire records in host memory on both sides, bounded pieces
-//   fixed_base.hip  one base, a window table of its multiples, no doublings per scalar (fixed_base.hpp: the program shared with the host)
+//   fixed_base.hip  one base, a window table of its multiples, no doublings per scalar (fixed_base.hpp: the program shared with the host);
+//                   table sets over several G1 bases and linear combinations over them, sliced over lanes (the slice plan)
 //   (msm_g1.hip, msm_g2.hip, msm_partition.hip, ntt.hip, point_fft*.hip, codec.hip, field_ops.hip, records.hip: the kernels behind the functions declared below)
 #pragma once
 #include <hip/hip_runtime.h>

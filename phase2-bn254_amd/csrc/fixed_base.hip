@@ -3,6 +3,8 @@
 // multiples of ONE generator.  The table is built once per base by the existing per-point batch_exp (4096 scalars j * 2^(8 w) mod r over the
 // same base: no new curve kernel); a multiplication is then one lane per scalar, at most 32 mixed additions from gathered table entries
 // into a U-form Jacobian accumulator, X and Y parked in the output record and Z in scratch, and the batched normalisation of batch_exp.
+// A table SET over several G1 bases (one batch_exp builds all of it) serves linear combinations first + sum_j k[i][j] P_j, one lane per
+// (row, slice of bases): the input accumulators of groth16/verifier.rs:44-48 for many proofs against one verifying key.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -51,6 +53,54 @@ __global__ void __launch_bounds__(256) fixed_base_mul_kernel(typename G::Aff* __
   const Jacobian<typename G::Z> r = G::to_std(acc);
   out[i] = typename G::Aff{r.x, r.y};
   zbuf[i] = r.z;
+}
+
+// ---- out[i] = first + sum_j k[i][j] * P_j over a table SET (table j at entry j * FB_ENTRIES): one lane per (row, slice of slice_len
+// consecutive bases), lane t = slice * n + row, so a wave's lanes share their slice and walk the same number of bases.  A lane runs the
+// fixed-base program once per base of its slice into ONE accumulator.  n_slices == 1: the lane adds `first` and parks X, Y in out[row], Z
+// in zbuf[row] (batch_normalize_g1 finishes the record).  Otherwise the slice's sum goes to partial[t] as a Jacobian record and
+// fixed_bases_join_kernel adds a row's slices.  row < n, slice < n_slices; the last slice may be short.
+__global__ void __launch_bounds__(256) fixed_bases_lincomb_kernel(G1Affine* __restrict__ out, const G1Affine* __restrict__ tables, uint64_t n_bases,
+                                                                 const G1Affine* __restrict__ first, const uint32_t* __restrict__ scalars, uint64_t n,
+                                                                 uint64_t slice_len, uint64_t n_slices, Fq* __restrict__ zbuf,
+                                                                 G1Jacobian* __restrict__ partial) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n * n_slices) return;
+  const uint64_t slice = t / n, row = t - slice * n;
+  const uint64_t j0 = slice * slice_len, j1 = j0 + slice_len < n_bases ? j0 + slice_len : n_bases;
+  G1U::Acc acc = G1U::Acc::zero();
+#pragma unroll 1
+  for (uint64_t j = j0; j < j1; ++j) {
+    uint32_t k[8];
+    {
+      const uint4* sp = reinterpret_cast<const uint4*>(scalars + (row * n_bases + j) * 8);
+      const uint4 s0 = sp[0], s1 = sp[1];
+      k[0] = s0.x; k[1] = s0.y; k[2] = s0.z; k[3] = s0.w; k[4] = s1.x; k[5] = s1.y; k[6] = s1.z; k[7] = s1.w;
+    }
+    const G1Affine* table = tables + j * (uint64_t)FB_ENTRIES;
+    fixed_base_accumulate<G1U>(acc, k, [&](uint32_t index) { return load_record(table + index); });
+  }
+  if (n_slices == 1) {
+    if (first) fixed_base_add(acc, load_record(first), false);
+    const G1Jacobian r = G1U::to_std(acc);
+    out[row] = G1Affine{r.x, r.y};
+    zbuf[row] = r.z;
+  } else {
+    partial[t] = G1U::to_std(acc);
+  }
+}
+
+// out[row] = (X, Y), zbuf[row] = Z of first + sum over the slices of partial[slice * n + row]: the reference's Jacobian addition (jac_add:
+// equal, opposite and infinite operands handled), one lane per row
+__global__ void __launch_bounds__(256) fixed_bases_join_kernel(G1Affine* __restrict__ out, const G1Affine* __restrict__ first, uint64_t n,
+                                                              uint64_t n_slices, Fq* __restrict__ zbuf, const G1Jacobian* __restrict__ partial) {
+  const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n) return;
+  G1Jacobian acc = first ? affine_to_jacobian(load_record(first)) : G1Jacobian::zero();
+#pragma unroll 1
+  for (uint64_t s = 0; s < n_slices; ++s) jac_add(acc, partial[s * n + row]);
+  out[row] = G1Affine{acc.x, acc.y};
+  zbuf[row] = acc.z;
 }
 
 // (j << 8 w) mod r, canonical: the value is below 2^255 < 3 r
@@ -135,6 +185,115 @@ int table_mul(void* d_out, const void* d_table, const void* d_scalars, size_t n,
   return ZK_OK;
 }
 
+// ---- a table SET over n_bases G1 bases, and linear combinations over it
+// A row's bases are cut into slices so that one row over a thousand bases does not run on one lane.  Two measured costs set the cut
+// (profiles/verify_proofs.md: the A/B): a lane spends about as long on ONE base as the join spends on FB_JOIN_PER_BASE slices, so a
+// row's critical path slice_len + n_bases / (FB_JOIN_PER_BASE slice_len) is shortest at slice_len = sqrt(n_bases / FB_JOIN_PER_BASE); and
+// past MI355ZK_FIXED_BASES_LANE_TARGET lanes more slices only queue behind one another, so the rows are never cut into more than reach it,
+// and not at all when they reach it alone.  Host arithmetic.
+constexpr size_t FB_JOIN_PER_BASE = 16;
+int bases_plan(size_t n, size_t n_bases, size_t* slice_len, size_t* n_slices) {
+  if (!slice_len || !n_slices || n >= ((size_t)1 << 31)) return ZK_ERR_BAD_ARGS;
+  if (n_bases == 0) {
+    *slice_len = 1;
+    *n_slices = 0;
+    return ZK_OK;
+  }
+  const size_t target = MI355ZK_FIXED_BASES_LANE_TARGET, rows = n ? n : 1;
+  size_t want = rows >= target ? 1 : (target + rows - 1) / rows;   // rows * want < target + rows < 2^31
+  if (want > n_bases) want = n_bases;
+  size_t len = (n_bases + want - 1) / want, balance = 1;
+  if (n_bases < ((size_t)1 << 31))                                 // (no table set is longer: the loop stays short)
+    while (balance * balance * FB_JOIN_PER_BASE < n_bases) ++balance;   // ceil(sqrt(n_bases / FB_JOIN_PER_BASE))
+  *slice_len = len > balance ? len : balance;
+  *n_slices = (n_bases + *slice_len - 1) / *slice_len;
+  return ZK_OK;
+}
+
+size_t bases_table_bytes(size_t n_bases) {
+  const size_t one = (size_t)FB_ENTRIES * sizeof(G1Affine);
+  return n_bases > (((size_t)1 << 31) - 1) / FB_ENTRIES ? 0 : n_bases * one;   // the build's batch_exp indexes its terms with 32 bits
+}
+
+int bases_build(void* d_tables, size_t table_bytes, const uint64_t* bases_raw, size_t n_bases, void* stream) {
+  if (n_bases == 0) return ZK_OK;
+  const size_t need = bases_table_bytes(n_bases);
+  if (!d_tables || !bases_raw || need == 0 || table_bytes < need) return ZK_ERR_BAD_ARGS;
+  std::vector<G1Affine> bases(n_bases);
+  std::memcpy(bases.data(), bases_raw, n_bases * sizeof(G1Affine));
+  for (const G1Affine& b : bases)                          // the identity is a base like any other here: its table is all zero
+    if (!b.is_zero() && !g1_on_curve_host(b)) return ZK_ERR_BAD_ARGS;
+  const size_t total = n_bases * (size_t)FB_ENTRIES;
+  std::vector<uint32_t> ks(total * 8), index(total);
+  for (int w = 0; w < FB_WINDOWS; ++w)
+    for (int j = 1; j <= FB_HALF; ++j) table_scalar(w, j, &ks[((size_t)w * FB_HALF + (j - 1)) * 8]);
+  for (size_t b = 0; b < n_bases; ++b) {
+    if (b) std::memcpy(&ks[b * FB_ENTRIES * 8], ks.data(), (size_t)FB_ENTRIES * 32);
+    for (size_t e = 0; e < (size_t)FB_ENTRIES; ++e) index[b * FB_ENTRIES + e] = (uint32_t)b;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  void* d_in = nullptr;                                     // the bases, the scalars, the base index (one-time work: a plain allocation)
+  const size_t bases_bytes = (n_bases * sizeof(G1Affine) + 255) & ~(size_t)255, ks_bytes = total * 32;
+  ZK_HIP(hipMalloc(&d_in, bases_bytes + ks_bytes + total * 4));
+  char* d = (char*)d_in;
+  int rc = ZK_OK;
+  if (hipMemcpyAsync(d, bases.data(), n_bases * sizeof(G1Affine), hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(d + bases_bytes, ks.data(), ks_bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(d + bases_bytes + ks_bytes, index.data(), total * 4, hipMemcpyHostToDevice, st) != hipSuccess)
+    rc = ZK_ERR_DEVICE;
+  if (rc == ZK_OK) rc = batch_exp<Fq>(d_tables, d, 0, d + bases_bytes, 0, total, stream, (const uint32_t*)(d + bases_bytes + ks_bytes));
+  if (hipStreamSynchronize(st) != hipSuccess && rc == ZK_OK) rc = ZK_ERR_DEVICE;
+  (void)hipFree(d_in);
+  return rc;
+}
+
+int bases_lincomb(void* d_out, const void* d_tables, size_t n_bases, const void* d_first, const void* d_scalars, size_t n, size_t slice_len,
+                  void* stream) {
+  if (n == 0) return ZK_OK;
+  if (!d_out || n >= ((size_t)1 << 31) || (n_bases && (!d_tables || !d_scalars))) return ZK_ERR_BAD_ARGS;
+  if (n_bases && (bases_table_bytes(n_bases) == 0 || n > ((size_t)-1) / 32 / n_bases)) return ZK_ERR_BAD_ARGS;
+  size_t n_slices = 0;
+  if (slice_len == 0) {
+    const int rc = bases_plan(n, n_bases, &slice_len, &n_slices);
+    if (rc) return rc;
+  } else {
+    if (slice_len > n_bases) slice_len = n_bases ? n_bases : 1;
+    n_slices = (n_bases + slice_len - 1) / slice_len;
+  }
+  if (n_slices >= ((size_t)1 << 31) || n * n_slices >= ((size_t)1 << 31)) return ZK_ERR_BAD_ARGS;
+  hipStream_t st = (hipStream_t)stream;
+  // chunks of at most 2^18 lanes, as table_mul launches them (a row's slices stay in one launch); the Z and partial-sum scratch is one
+  // chunk's, reused in stream order
+  const size_t lanes_max = (size_t)1 << 18, per_row = n_slices > 1 ? n_slices : 1;
+  size_t chunk = lanes_max / per_row;
+  chunk = chunk < 1 ? 1 : chunk;
+  chunk = n < chunk ? n : chunk;
+  const size_t z_bytes = (chunk * sizeof(Fq) + 255) & ~(size_t)255;
+  const size_t part_bytes = n_slices > 1 ? chunk * n_slices * sizeof(G1Jacobian) : 0;
+  std::lock_guard<std::mutex> launch_lk(g_exp_launch_mu);
+  void* scratch = nullptr;
+  int rc = exp_scratch(z_bytes + part_bytes, stream, &scratch);
+  if (rc) return rc;
+  Fq* zbuf = (Fq*)scratch;
+  G1Jacobian* partial = (G1Jacobian*)((char*)scratch + z_bytes);
+  for (size_t i0 = 0; i0 < n; i0 += chunk) {
+    const size_t m = n - i0 < chunk ? n - i0 : chunk;
+    G1Affine* out = (G1Affine*)d_out + i0;
+    const size_t lanes = m * n_slices;
+    if (lanes)
+      hipLaunchKernelGGL(fixed_bases_lincomb_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, out, (const G1Affine*)d_tables,
+                         (uint64_t)n_bases, (const G1Affine*)d_first, (const uint32_t*)d_scalars + i0 * n_bases * 8, (uint64_t)m,
+                         (uint64_t)slice_len, (uint64_t)n_slices, zbuf, partial);
+    if (n_slices != 1)
+      hipLaunchKernelGGL(fixed_bases_join_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, out, (const G1Affine*)d_first, (uint64_t)m,
+                         (uint64_t)n_slices, zbuf, (const G1Jacobian*)partial);
+    ZK_HIP(hipGetLastError());
+    rc = batch_normalize_g1(out, zbuf, m, st);
+    if (rc) return rc;
+  }
+  return ZK_OK;
+}
+
 // ---- the host run of the same program: every entry it needs comes from a plain host scalar multiplication by the table's scalar
 // (j << 8 w) mod r (MSB first, leading zeros skipped), kept per base so that a test over many scalars computes an entry once.
 template <class F>
@@ -159,31 +318,39 @@ Affine<F> host_entry(const Affine<F>& base, uint32_t index) {
   return a;
 }
 
+// the entries of one base, computed on demand and kept by the base's bytes (a handful of bases at most).  The caller holds g_host_mu.
+template <class A>
+struct HostCache {
+  std::vector<A> entry = std::vector<A>(FB_ENTRIES);
+  std::vector<uint8_t> have = std::vector<uint8_t>(FB_ENTRIES, 0);
+};
+std::mutex g_host_mu;
 template <class G>
-int host_mul(const uint64_t* base_raw, const uint64_t k_raw[4], uint64_t* out_raw) {
+HostCache<typename G::Aff>& host_cache(const uint64_t* base_raw) {
   using A = typename G::Aff;
-  using F = typename G::Z;
-  A base;
-  std::memcpy(&base, base_raw, sizeof base);
-  if (!base_in_group(base)) return ZK_ERR_BAD_ARGS;
-  struct Cache {
-    std::vector<A> entry = std::vector<A>(FB_ENTRIES);
-    std::vector<uint8_t> have = std::vector<uint8_t>(FB_ENTRIES, 0);
-  };
-  static std::mutex mu;
-  static std::map<std::vector<uint64_t>, Cache> cache;      // by the base's bytes; a handful of bases at most
-  std::lock_guard<std::mutex> lk(mu);
+  static std::map<std::vector<uint64_t>, HostCache<A>> cache;
+  const std::vector<uint64_t> key(base_raw, base_raw + sizeof(A) / 8);
+  auto it = cache.find(key);
+  if (it != cache.end()) return it->second;
   if (cache.size() >= 8) cache.clear();
-  Cache& c = cache[std::vector<uint64_t>(base_raw, base_raw + sizeof(A) / 8)];
+  return cache[key];
+}
+template <class G>
+void host_accumulate(typename G::Acc& acc, const typename G::Aff& base, HostCache<typename G::Aff>& c, const uint64_t k_raw[4]) {
   uint32_t k[8];
   std::memcpy(k, k_raw, 32);
-  const typename G::Acc acc = fixed_base_run<G>(k, [&](uint32_t index) {
+  fixed_base_accumulate<G>(acc, k, [&](uint32_t index) {
     if (!c.have[index]) {
-      c.entry[index] = host_entry<F>(base, index);
+      c.entry[index] = host_entry<typename G::Z>(base, index);
       c.have[index] = 1;
     }
     return c.entry[index];
   });
+}
+template <class G>
+void host_finish(const typename G::Acc& acc, uint64_t* out_raw) {
+  using A = typename G::Aff;
+  using F = typename G::Z;
   const Jacobian<F> r = G::to_std(acc);
   A a{F::zero(), F::zero()};
   if (!r.is_zero()) {
@@ -192,6 +359,38 @@ int host_mul(const uint64_t* base_raw, const uint64_t k_raw[4], uint64_t* out_ra
     a.y = mul(r.y, mul(zi2, zi));
   }
   std::memcpy(out_raw, &a, sizeof a);
+}
+
+template <class G>
+int host_mul(const uint64_t* base_raw, const uint64_t k_raw[4], uint64_t* out_raw) {
+  typename G::Aff base;
+  std::memcpy(&base, base_raw, sizeof base);
+  if (!base_in_group(base)) return ZK_ERR_BAD_ARGS;
+  std::lock_guard<std::mutex> lk(g_host_mu);
+  typename G::Acc acc = G::Acc::zero();
+  host_accumulate<G>(acc, base, host_cache<G>(base_raw), k_raw);
+  host_finish<G>(acc, out_raw);
+  return ZK_OK;
+}
+
+// one row of bases_lincomb on the host: the program of the one-slice lane (every base into one accumulator, then `first`)
+int host_lincomb(const uint64_t* bases_raw, size_t n_bases, const uint64_t* first_raw, const uint64_t* scalars, uint64_t out_raw[8]) {
+  if (!out_raw || (n_bases && (!bases_raw || !scalars))) return ZK_ERR_BAD_ARGS;
+  std::vector<G1Affine> bases(n_bases);
+  if (n_bases) std::memcpy(bases.data(), bases_raw, n_bases * sizeof(G1Affine));
+  for (const G1Affine& b : bases)
+    if (!b.is_zero() && !g1_on_curve_host(b)) return ZK_ERR_BAD_ARGS;
+  std::lock_guard<std::mutex> lk(g_host_mu);
+  G1U::Acc acc = G1U::Acc::zero();
+  for (size_t j = 0; j < n_bases; ++j)
+    if (!bases[j].is_zero())                                // (the identity's table is all zero: every entry is skipped)
+      host_accumulate<G1U>(acc, bases[j], host_cache<G1U>(bases_raw + 8 * j), scalars + 4 * j);
+  if (first_raw) {
+    G1Affine first;
+    std::memcpy(&first, first_raw, sizeof first);
+    fixed_base_add(acc, first, false);
+  }
+  host_finish<G1U>(acc, out_raw);
   return ZK_OK;
 }
 
@@ -214,6 +413,21 @@ int mi355zk_bn254_g1_fixed_base_mul_dev(void* d_out_affine, const void* d_table,
 }
 int mi355zk_bn254_g2_fixed_base_mul_dev(void* d_out_affine, const void* d_table, const void* d_scalars, size_t n, uint32_t flags, void* stream) {
   return zk::abi_guard([&]() -> int { return zk::table_mul<zk::G2U>(d_out_affine, d_table, d_scalars, n, flags, stream); });
+}
+size_t mi355zk_fixed_bases_table_bytes(size_t n_bases) { return zk::bases_table_bytes(n_bases); }
+int mi355zk_fixed_bases_plan(size_t n, size_t n_bases, size_t* slice_len, size_t* n_slices) {
+  return zk::abi_guard([&]() -> int { return zk::bases_plan(n, n_bases, slice_len, n_slices); });
+}
+int mi355zk_bn254_g1_fixed_bases_build_dev(void* d_tables, size_t table_bytes, const uint64_t* bases_affine, size_t n_bases, void* stream) {
+  return zk::abi_guard([&]() -> int { return zk::bases_build(d_tables, table_bytes, bases_affine, n_bases, stream); });
+}
+int mi355zk_bn254_g1_fixed_bases_lincomb_dev(void* d_out_affine, const void* d_tables, size_t n_bases, const void* d_first_affine,
+                                             const void* d_scalars, size_t n, size_t slice_len, void* stream) {
+  return zk::abi_guard([&]() -> int { return zk::bases_lincomb(d_out_affine, d_tables, n_bases, d_first_affine, d_scalars, n, slice_len, stream); });
+}
+int mi355zk_selftest_fixed_bases_lincomb(const uint64_t* bases_affine, size_t n_bases, const uint64_t* first_affine, const uint64_t* scalars,
+                                         uint64_t out_affine[8]) {
+  return zk::abi_guard([&]() -> int { return zk::host_lincomb(bases_affine, n_bases, first_affine, scalars, out_affine); });
 }
 int mi355zk_selftest_fixed_base_digits(const uint64_t k[4], int16_t digits[32]) {
   return zk::abi_guard([&]() -> int {

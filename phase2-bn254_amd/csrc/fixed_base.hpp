@@ -5,8 +5,9 @@
 // j = 1 .. FB_HALF, affine raw records (4096 entries: 256 KiB for G1, 512 KiB for G2), so a scalar costs NO doubling and at most FB_WINDOWS
 // mixed additions:  k = sum_w d_w 2^(8 w),  d_w in [-128, 128],  k P = sum_w sign(d_w) T[w][|d_w| - 1].
 // The additions are the general routines of curveu.hpp (equal, opposite and infinite operands handled), NOT a stripped variant: for a
-// canonical k the partial sum never equals MINUS the entry being added (that would make k == 0 mod r), but it can EQUAL it -- exactly
-// for k = 2 * 48 * 2^248 - r, whose low windows sum to 48 * 2^248 - r == 48 * 2^248 (mod r) -- and jacu_add_mixed then doubles.
+// canonical k over ONE base the partial sum never equals MINUS the entry being added (that would make k == 0 mod r), but it can EQUAL it --
+// exactly for k = 2 * 48 * 2^248 - r, whose low windows sum to 48 * 2^248 - r == 48 * 2^248 (mod r) -- and jacu_add_mixed then doubles.
+// Over several bases (fixed_base_accumulate) all of these cases are ordinary.
 #pragma once
 
 #include "window_mul.hpp"
@@ -52,16 +53,25 @@ ZK_HD void fixed_base_add(JacU2& acc, const G2Affine& e, bool negate) {
   jacu2_add_tab(acc, t, negate);
 }
 
-// k * P: FB_WINDOWS steps of "digit, load entry, add", zero digits skipped.  load(index) returns the affine entry at a table index.
+// acc += k * P: FB_WINDOWS steps of "digit, load entry, add", zero digits skipped.  load(index) returns the affine entry at a table index.
+// The accumulator is the caller's, so a sum over SEVERAL bases (fixed_bases_lincomb_kernel, one table per base) runs this once per base into
+// one accumulator.  There the partial sum is whatever the earlier bases left: it can equal the entry, be its negative (the sum passes through
+// the identity) or be the identity in the middle of a row, and the general additions above take all three.
 template <class G, class Load>
-ZK_HD typename G::Acc fixed_base_run(const uint32_t (&k)[8], Load&& load) {
-  typename G::Acc acc = G::Acc::zero();
+ZK_HD void fixed_base_accumulate(typename G::Acc& acc, const uint32_t (&k)[8], Load&& load) {
   uint32_t carry = 0;
 #pragma unroll 1
   for (int w = 0; w < FB_WINDOWS; ++w) {
     const int d = fixed_base_digit(k, w, carry);
     if (d != 0) fixed_base_add(acc, load(fixed_base_index(w, d)), d < 0);
   }
+}
+
+// k * P: the same from the identity
+template <class G, class Load>
+ZK_HD typename G::Acc fixed_base_run(const uint32_t (&k)[8], Load&& load) {
+  typename G::Acc acc = G::Acc::zero();
+  fixed_base_accumulate<G>(acc, k, load);
   return acc;
 }
 

@@ -20,6 +20,7 @@ NO_FLAG, PIN_TABLES = (1 << 64) - 1, 1   # MI355ZK_NO_FLAG (inf_off: no infinity
 ABI_VERSION = 7   # MI355ZK_ABI_VERSION of the include/mi355zk.h this table was written against: load() refuses another library
 H_INTO_REPR = 1   # MI355ZK_H_INTO_REPR: flags of fr_h_poly[_dev]
 FIXED_SCALARS_MONTGOMERY = 1   # MI355ZK_FIXED_SCALARS_MONTGOMERY: flags of fixed_base_mul_dev
+FIXED_BASES_LANE_TARGET = 262144  # MI355ZK_FIXED_BASES_LANE_TARGET: the lane count mi355zk_fixed_bases_plan aims for
 EXP_SAME_SCALAR, FFT_INVERSE, G2_TRUSTED_SUBGROUP = 1, 1, 2   # mode / flag bits of batch_exp, point_fft, sparse_matvec (include/mi355zk.h)
 
 _vp, _sz, _i, _u32 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32
@@ -129,6 +130,11 @@ SIGNATURES = {
     "mi355zk_bn254_g2_fixed_base_build_dev": (_i, [_vp, _sz, _vp, _vp]),
     "mi355zk_bn254_g1_fixed_base_mul_dev": (_i, [_vp, _vp, _vp, _sz, _u32, _vp]),
     "mi355zk_bn254_g2_fixed_base_mul_dev": (_i, [_vp, _vp, _vp, _sz, _u32, _vp]),
+    "mi355zk_fixed_bases_table_bytes": (_sz, [_sz]),
+    "mi355zk_fixed_bases_plan": (_i, [_sz, _sz, C.POINTER(_sz), C.POINTER(_sz)]),
+    "mi355zk_bn254_g1_fixed_bases_build_dev": (_i, [_vp, _sz, _vp, _sz, _vp]),
+    "mi355zk_bn254_g1_fixed_bases_lincomb_dev": (_i, [_vp, _vp, _sz, _vp, _vp, _sz, _sz, _vp]),
+    "mi355zk_selftest_fixed_bases_lincomb": (_i, [_vp, _sz, _vp, _vp, _vp]),
     "mi355zk_selftest_fixed_base_digits": (_i, [_vp, _vp]),
     "mi355zk_selftest_fixed_base_mul": (_i, [_i, _vp, _vp, _vp]),
     "mi355zk_bn254_g1_batch_exp": (_i, [_vp, _vp, _vp, _sz, _i]),
