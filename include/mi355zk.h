@@ -607,6 +607,43 @@ int mi355zk_bn254_g2_accumulator_power_pairs(const uint8_t *in, size_t n, int co
                                              uint64_t stream_id, uint64_t first, uint8_t *out_uncompressed, size_t piece, uint64_t out_s[24],
                                              uint64_t out_sx[24], long long *err_index);
 
+/* ---- whole vectors between a file and the device: n WIRE records in host memory (typically an mmap'ed file range, pageable, `in` may be
+ * read-only) <-> n raw affine records (64 / 128 B) in the CALLER's device vector, which stays on the device for the transforms that follow
+ * (powersoftau/src/bin/prepare_phase2.rs reads each accumulator vector once and writes its Lagrange form for every degree).  The work runs in
+ * pieces of `piece` records (0 = 2^18) over two buffer sets, a copy and a compute stream of the calling thread's current device: the upload
+ * (download) of one piece overlaps the decoding (encoding) of the next.  Device memory beyond the caller's vector, with P = min(piece, n):
+ *   points_load   2 (P (in_record + 1 under check_subgroup) + 256) B     points_store   2 P out_record B
+ * (each term rounded up to 256 B), never a function of n; in_record / out_record = 64 / 128 B uncompressed, 32 / 64 B compressed.
+ * points_load: d_out[i] = decode(in[i]) with the codec kernels above (checked: into_affine instead of into_affine_unchecked).  A record the
+ *   decoder refuses returns the decoder's code (4, 6, 7, 8), an all-zero decoded record MI355ZK_ERR_POINT_AT_INFINITY (read_points_chunk,
+ *   batched_accumulator.rs:938-983), under check_subgroup (G2 only; ignored for G1) a record outside the order-r subgroup 5; *err_index (may
+ *   be NULL) is then the lowest such index, within the call, of the first piece that fails -- later pieces are not looked at -- and -1
+ *   otherwise.  Within a piece the order is: decoding, infinity, membership.  On a non-zero return the contents of d_out are unspecified.
+ * points_store: out[i] = encode(d_in[i]); the all-zero record is written as the codec writes infinity.
+ * Both: 3 = a NULL pointer with n > 0, a device pointer that is not 16-byte aligned, piece >= 2^31; n == 0 succeeds and does nothing.
+ * Synchronous: they return after the last piece has completed, and they do NOT order themselves after work queued on any other stream -- the
+ * caller synchronises the stream that produced d_in (or will consume d_out) itself.  Re-entrant from several host threads. */
+int mi355zk_bn254_g1_points_load(void *d_out_affine, const uint8_t *in, size_t n, int compressed, int checked, int check_subgroup, size_t piece,
+                                 long long *err_index);
+int mi355zk_bn254_g2_points_load(void *d_out_affine, const uint8_t *in, size_t n, int compressed, int checked, int check_subgroup, size_t piece,
+                                 long long *err_index);
+int mi355zk_bn254_g1_points_store(uint8_t *out, const void *d_in_affine, size_t n, int compressed, size_t piece);
+int mi355zk_bn254_g2_points_store(uint8_t *out, const void *d_in_affine, size_t n, int compressed, size_t piece);
+
+/* ---- the H bases of prepare_phase2.rs:137-147: out[i] = in[i + shift] - in[i], i < n_out, on raw affine G1 records (64 B, all-zero =
+ * infinity); the output is affine and normalised, byte for byte what the two-term rows of mi355zk_bn254_g1_sparse_matvec_dev give, without
+ * their index and coefficient arrays (72 B per output).  One affine chord per output -- the tangent at in[i + shift] when
+ * in[i + shift] == -in[i], infinity when the two are equal, the other operand (negated for in[i]) when one is infinity -- and one field
+ * inversion per MI355ZK_SHIFTED_DIFFERENCE_K consecutive outputs.  No device memory beyond the two vectors.  DOMAIN: points on the curve;
+ * nothing is tested and nothing faults outside it.  Asynchronous on `stream`.
+ * 3 = shift == 0, shift + n_out > n_in, out[0, n_out) overlapping in[0, n_in), and with n_out > 0 a NULL or not 16-byte aligned pointer;
+ * n_out == 0 succeeds and launches nothing.  There is no G2 twin: the H bases are G1 only.
+ * mi355zk_selftest_g1_shifted_difference: the same lane routine, with the same grouping into shared inversions, run on HOST records (no
+ * device needed; 8-byte alignment suffices). */
+#define MI355ZK_SHIFTED_DIFFERENCE_K 16
+int mi355zk_bn254_g1_shifted_difference_dev(void *d_out_affine, const void *d_in_affine, size_t n_in, size_t shift, size_t n_out, void *stream);
+int mi355zk_selftest_g1_shifted_difference(uint64_t *out, const uint64_t *in, size_t n_in, size_t shift, size_t n_out);
+
 /* ---- the pairing e: G1 x G2 -> GT (Engine::miller_loop + final_exponentiation, pairing/src/bn256/mod.rs:57-226) in its batched form: many
  * independent pairing PRODUCTS in one call -- every same_ratio of a verify_transformation (powersoftau/src/utils.rs:151-159), the four
  * pairings per contribution of MPCParameters::verify (phase2/src/parameters.rs:529-659), the three-pair product of each of many proofs

@@ -142,6 +142,11 @@ extern "C" {
     pub fn mi355zk_bn254_g2_accumulator_transform(out: *mut u8, in_: *const u8, n: usize, first: u64, tau: *const u64 /* [4] */, coeff: *const u64 /* [4] */, in_compressed: c_int, out_compressed: c_int, checked: c_int, mode: u32, piece: usize, err_index: *mut c_longlong) -> c_int;
     pub fn mi355zk_bn254_g1_accumulator_power_pairs(in_: *const u8, n: usize, compressed: c_int, checked: c_int, check_subgroup: c_int, key: *const u32 /* [8] */, stream_id: u64, first: u64, out_uncompressed: *mut u8, piece: usize, out_s: *mut u64 /* [12] */, out_sx: *mut u64 /* [12] */, err_index: *mut c_longlong) -> c_int;
     pub fn mi355zk_bn254_g2_accumulator_power_pairs(in_: *const u8, n: usize, compressed: c_int, checked: c_int, check_subgroup: c_int, key: *const u32 /* [8] */, stream_id: u64, first: u64, out_uncompressed: *mut u8, piece: usize, out_s: *mut u64 /* [24] */, out_sx: *mut u64 /* [24] */, err_index: *mut c_longlong) -> c_int;
+    pub fn mi355zk_bn254_g1_points_load(d_out_affine: *mut c_void, in_: *const u8, n: usize, compressed: c_int, checked: c_int, check_subgroup: c_int, piece: usize, err_index: *mut c_longlong) -> c_int;
+    pub fn mi355zk_bn254_g2_points_load(d_out_affine: *mut c_void, in_: *const u8, n: usize, compressed: c_int, checked: c_int, check_subgroup: c_int, piece: usize, err_index: *mut c_longlong) -> c_int;
+    pub fn mi355zk_bn254_g1_points_store(out: *mut u8, d_in_affine: *const c_void, n: usize, compressed: c_int, piece: usize) -> c_int;
+    pub fn mi355zk_bn254_g2_points_store(out: *mut u8, d_in_affine: *const c_void, n: usize, compressed: c_int, piece: usize) -> c_int;
+    pub fn mi355zk_bn254_g1_shifted_difference_dev(d_out_affine: *mut c_void, d_in_affine: *const c_void, n_in: usize, shift: usize, n_out: usize, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_pairing_product_dev(d_gt_out: *mut c_void, d_g1_affine: *const c_void, d_g2_affine: *const c_void, n_pairs: usize, d_group_ptr: *const u32, n_groups: usize, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_gt_is_one_dev(d_flags: *mut u8, d_gt: *const c_void, n: usize, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_gt_eq_dev(d_flags: *mut u8, d_gt_a: *const c_void, d_gt_b: *const c_void, n: usize, stream: *mut c_void) -> c_int;

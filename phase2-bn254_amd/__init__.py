@@ -10,7 +10,9 @@ Layout:
   verify.py       the ceremony steps and their checks: contribute_mpc_parameters, verify_contribution, verify_mpc_parameters,
                   contribute_response, verify_transform, next_challenge -- one pairing launch per verification
   stream.py       powers-of-tau files streamed through the device in bounded memory: batches, calculate_hash_file, new_constrained,
-                  compute_constrained, verify_transform_constrained (file to file, mmap'ed; the in-memory flows of verify.py are the yardstick)
+                  compute_constrained, verify_transform_constrained (file to file, mmap'ed; the in-memory flows of verify.py are the yardstick);
+                  prepare_phase2_plan, prepare_phase2_files (a response -> every phase1radix2m{k}, one vector on the device at a time),
+                  read_phase1radix2m_file, points_load / points_store (wire records in a mapping <-> a device vector)
   prover.py       the caller of the path: groth16 create_proof (prover.rs:202-343) over the device library
   ceremony.py     the ceremony-side callers (batch_exp, merge_pairs, QAP evaluation, point FFT, codecs, file containers)
   bellman.py      host-side mirror of the reference's interface for this path:
@@ -39,6 +41,11 @@ from .stream import (  # noqa: F401
     calculate_hash_file,
     compute_constrained,
     new_constrained,
+    points_load,
+    points_store,
+    prepare_phase2_files,
+    prepare_phase2_plan,
+    read_phase1radix2m_file,
     verify_transform_constrained,
 )
 from .verify import (  # noqa: F401

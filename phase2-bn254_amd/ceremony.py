@@ -259,6 +259,26 @@ def point_ifft(points, trusted_subgroup: bool = False):
     return _point_fft(points, 1, trusted_subgroup)
 
 
+def shifted_difference(points, shift: int, n_out: int, out=None):
+    """out[i] = points[i + shift] - points[i], i < n_out, on (n, 8) G1 records: mi355zk_bn254_g1_shifted_difference_dev, one affine chord
+    per output and one inversion per lib.SHIFTED_DIFFERENCE_K of them.  With shift = m and n_out = m - 1 these are the H bases of
+    prepare_phase2.rs:137-147, byte for byte those of prepare_phase2 below, with no index or coefficient arrays.  out: a contiguous
+    (>= n_out, 8) tensor that does not overlap `points` to write into (its first n_out rows are returned); a new one when None."""
+    import torch
+
+    if _group(points) != 1 or not points.is_contiguous():
+        raise ValueError("shifted_difference: contiguous (n, 8) G1 records")
+    if shift < 1 or n_out < 0 or shift + n_out > points.shape[0]:
+        raise ValueError("shifted_difference: 1 <= shift and shift + n_out <= the number of points")
+    if out is None:
+        out = torch.empty((n_out, 8), dtype=points.dtype, device=points.device)
+    elif _group(out) != 1 or not out.is_contiguous() or out.shape[0] < n_out or out.dtype != points.dtype:
+        raise ValueError("shifted_difference: out must be contiguous (>= n_out, 8) records")
+    out = out[:n_out]
+    _check(_lib.load().mi355zk_bn254_g1_shifted_difference_dev(_p(out), _p(points), points.shape[0], shift, n_out, _stream_ptr()), "shifted_difference")
+    return out
+
+
 _ENC_SIZE = {(1, False): 64, (1, True): 32, (2, False): 128, (2, True): 64}
 
 

@@ -236,6 +236,112 @@ int accumulator_power_pairs(const uint8_t* in, size_t n, int compressed, int che
   return ZK_OK;
 }
 
+// Wire records in host memory -> a vector of raw affine records that stays on the device (mi355zk_bn254_g{1,2}_points_load): the decoder
+// writes each piece straight into the caller's vector, so a buffer set holds the piece's wire bytes, its membership bytes and the four words.
+//
+//   copy stream      upload i+1 |               words i | upload i+2 ...
+//   compute stream   piece i:  decode -> (G2 membership) -> infinity scan
+template <int GROUP>
+int points_load(void* d_out, const uint8_t* in, size_t n, int compressed, int checked, int check_subgroup, size_t piece, long long* err_index) {
+  constexpr size_t rec = GROUP == 1 ? 64 : 128;
+  if (err_index) *err_index = -1;
+  if (piece == 0) piece = DEFAULT_PIECE;
+  if (piece >= ((size_t)1 << 31) || n > (~(size_t)0) / rec) return ZK_ERR_BAD_ARGS;
+  if (n == 0) return ZK_OK;
+  if (!d_out || !in || (uintptr_t)d_out % 16 != 0) return ZK_ERR_BAD_ARGS;
+  const bool membership = GROUP == 2 && check_subgroup != 0;
+  const size_t in_rec = compressed ? rec / 2 : rec;
+  const size_t m_max = n < piece ? n : piece;
+  const size_t o_mem = al256(m_max * in_rec), o_err = o_mem + (membership ? al256(m_max) : 0), set_bytes = o_err + 256;
+  int dev = 0;
+  ZK_HIP(hipGetDevice(&dev));
+  Events ev(4);   // (declared before the lease: destroyed after both streams are idle)
+  hipEvent_t* up = &ev.e[0];
+  hipEvent_t* done = &ev.e[2];
+  CallLease lease;
+  int rc = lease.open(dev, 2 * set_bytes);
+  if (rc) return rc;
+  HostStage* S = lease.S;
+  char* set[2] = {(char*)lease.buf, (char*)lease.buf + set_bytes};
+  hipError_t e = ev.create();
+  if (e != hipSuccess) return hip_fail("points_load", e);
+  const size_t n_pieces = (n + piece - 1) / piece;
+  auto upload_and_launch = [&](size_t i) -> bool {   // false: rc, or else e, says why
+    const size_t p0 = i * piece, m = n - p0 < piece ? n - p0 : piece;
+    const int k = (int)(i & 1);
+    char* b = set[k];
+    char* dst = (char*)d_out + p0 * rec;
+    unsigned long long* w = (unsigned long long*)(b + o_err);
+    uint8_t* d_member = membership ? (uint8_t*)(b + o_mem) : nullptr;
+    if ((e = hipMemcpyAsync(b, in + p0 * in_rec, m * in_rec, hipMemcpyHostToDevice, S->copy)) != hipSuccess) return false;
+    if ((e = hipEventRecord(up[k], S->copy)) != hipSuccess || (e = hipStreamWaitEvent(S->compute, up[k], 0)) != hipSuccess) return false;
+    if ((e = hipMemsetAsync(w, 0xff, W_COUNT * 8, S->compute)) != hipSuccess) return false;
+    if ((rc = codec_decode_enqueue(GROUP, dst, b, m, compressed, checked, S->compute, w + W_DECODE))) return false;
+    if (membership && (rc = g2_subgroup_flags(dst, m, (void*)S->compute, d_member))) return false;
+    if ((rc = scan<GROUP>(dst, m, d_member, w + W_INFINITY, w + W_SUBGROUP, S->compute))) return false;
+    return (e = hipEventRecord(done[k], S->compute)) == hipSuccess;
+  };
+  for (size_t i = 0; i < 2 && i < n_pieces; ++i)
+    if (!upload_and_launch(i)) return rc ? rc : hip_fail("points_load", e);
+  for (size_t i = 0; i < n_pieces; ++i) {
+    const int k = (int)(i & 1);
+    unsigned long long w[W_COUNT];
+    if ((e = hipStreamWaitEvent(S->copy, done[k], 0)) != hipSuccess) return hip_fail("points_load", e);
+    if ((e = hipMemcpyAsync(w, set[k] + o_err, sizeof w, hipMemcpyDeviceToHost, S->copy)) != hipSuccess) return hip_fail("points_load", e);
+    if ((e = hipStreamSynchronize(S->copy)) != hipSuccess) return hip_fail("points_load", e);   // piece i is decoded; its buffers are free
+    if ((rc = piece_verdict(w, i * piece, err_index))) return rc;   // (the lease waits for what is still queued)
+    if (i + 2 < n_pieces && !upload_and_launch(i + 2)) return rc ? rc : hip_fail("points_load", e);
+  }
+  if ((e = hipStreamSynchronize(S->compute)) != hipSuccess) return hip_fail("points_load", e);
+  return ZK_OK;
+}
+
+// The inverse (mi355zk_bn254_g{1,2}_points_store): piece i + 1 is encoded while piece i crosses the link; a buffer set is the piece's wire bytes.
+template <int GROUP>
+int points_store(uint8_t* out, const void* d_in, size_t n, int compressed, size_t piece) {
+  constexpr size_t rec = GROUP == 1 ? 64 : 128;
+  if (piece == 0) piece = DEFAULT_PIECE;
+  if (piece >= ((size_t)1 << 31) || n > (~(size_t)0) / rec) return ZK_ERR_BAD_ARGS;
+  if (n == 0) return ZK_OK;
+  if (!out || !d_in || (uintptr_t)d_in % 16 != 0) return ZK_ERR_BAD_ARGS;
+  const size_t out_rec = compressed ? rec / 2 : rec;
+  const size_t m_max = n < piece ? n : piece;
+  const size_t set_bytes = al256(m_max * out_rec);
+  int dev = 0;
+  ZK_HIP(hipGetDevice(&dev));
+  Events ev(2);   // (declared before the lease: destroyed after both streams are idle)
+  hipEvent_t* done = &ev.e[0];
+  CallLease lease;
+  int rc = lease.open(dev, 2 * set_bytes);
+  if (rc) return rc;
+  HostStage* S = lease.S;
+  char* set[2] = {(char*)lease.buf, (char*)lease.buf + set_bytes};
+  hipError_t e = ev.create();
+  if (e != hipSuccess) return hip_fail("points_store", e);
+  const size_t n_pieces = (n + piece - 1) / piece;
+  auto launch = [&](size_t i) -> bool {
+    const size_t p0 = i * piece, m = n - p0 < piece ? n - p0 : piece;
+    const int k = (int)(i & 1);
+    if ((rc = codec_encode(GROUP, set[k], (const char*)d_in + p0 * rec, m, compressed, S->compute))) return false;
+    return (e = hipEventRecord(done[k], S->compute)) == hipSuccess;
+  };
+  for (size_t i = 0; i < 2 && i < n_pieces; ++i)
+    if (!launch(i)) return rc ? rc : hip_fail("points_store", e);
+  for (size_t i = 0; i < n_pieces; ++i) {
+    const size_t p0 = i * piece, m = n - p0 < piece ? n - p0 : piece;
+    const int k = (int)(i & 1);
+    if ((e = hipStreamWaitEvent(S->copy, done[k], 0)) != hipSuccess) return hip_fail("points_store", e);
+    if ((e = hipMemcpyAsync(out + p0 * out_rec, set[k], m * out_rec, hipMemcpyDeviceToHost, S->copy)) != hipSuccess) return hip_fail("points_store", e);
+    if ((e = hipStreamSynchronize(S->copy)) != hipSuccess) return hip_fail("points_store", e);   // piece i is on the host; its buffer is free
+    if (i + 2 < n_pieces && !launch(i + 2)) return rc ? rc : hip_fail("points_store", e);
+  }
+  return ZK_OK;
+}
+
+template int points_load<1>(void*, const uint8_t*, size_t, int, int, int, size_t, long long*);
+template int points_load<2>(void*, const uint8_t*, size_t, int, int, int, size_t, long long*);
+template int points_store<1>(uint8_t*, const void*, size_t, int, size_t);
+template int points_store<2>(uint8_t*, const void*, size_t, int, size_t);
 template int accumulator_transform<1>(uint8_t*, const uint8_t*, size_t, uint64_t, const uint64_t*, const uint64_t*, int, int, int, uint32_t, size_t, long long*);
 template int accumulator_transform<2>(uint8_t*, const uint8_t*, size_t, uint64_t, const uint64_t*, const uint64_t*, int, int, int, uint32_t, size_t, long long*);
 template int accumulator_power_pairs<1>(const uint8_t*, size_t, int, int, int, const uint32_t*, uint64_t, uint64_t, uint8_t*, size_t, uint64_t*, uint64_t*, long long*);

@@ -820,6 +820,29 @@ int mi355zk_bn254_g2_accumulator_power_pairs(const uint8_t* in, size_t n, int co
   });
 }
 
+int mi355zk_bn254_g1_points_load(void* d_out_affine, const uint8_t* in, size_t n, int compressed, int checked, int check_subgroup, size_t piece,
+                                 long long* err_index) {
+  return abi_guard([&]() -> int { return points_load<1>(d_out_affine, in, n, compressed, checked, check_subgroup, piece, err_index); });
+}
+int mi355zk_bn254_g2_points_load(void* d_out_affine, const uint8_t* in, size_t n, int compressed, int checked, int check_subgroup, size_t piece,
+                                 long long* err_index) {
+  return abi_guard([&]() -> int { return points_load<2>(d_out_affine, in, n, compressed, checked, check_subgroup, piece, err_index); });
+}
+int mi355zk_bn254_g1_points_store(uint8_t* out, const void* d_in_affine, size_t n, int compressed, size_t piece) {
+  return abi_guard([&]() -> int { return points_store<1>(out, d_in_affine, n, compressed, piece); });
+}
+int mi355zk_bn254_g2_points_store(uint8_t* out, const void* d_in_affine, size_t n, int compressed, size_t piece) {
+  return abi_guard([&]() -> int { return points_store<2>(out, d_in_affine, n, compressed, piece); });
+}
+
+// the H bases of prepare_phase2 (point_diff.hip)
+int mi355zk_bn254_g1_shifted_difference_dev(void* d_out_affine, const void* d_in_affine, size_t n_in, size_t shift, size_t n_out, void* stream) {
+  return abi_guard([&]() -> int { return g1_shifted_difference(d_out_affine, d_in_affine, n_in, shift, n_out, (hipStream_t)stream); });
+}
+int mi355zk_selftest_g1_shifted_difference(uint64_t* out, const uint64_t* in, size_t n_in, size_t shift, size_t n_out) {
+  return abi_guard([&]() -> int { return g1_shifted_difference_host(out, in, n_in, shift, n_out); });
+}
+
 // host-side group helpers (joining per-GPU partial sums, normalising results)
 int mi355zk_bn254_g1_add(uint64_t acc_xyz[12], const uint64_t other_xyz[12]) {
   return abi_guard([&]() -> int {

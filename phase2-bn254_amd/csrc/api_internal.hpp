@@ -8,6 +8,7 @@
 //   scalar_mul.hip  the scalar-multiplication kernels and their launchers: batch_exp / batch_mul / window-table build / G2 membership
 //   fr_random.hip   the random exponents of merge_pairs generated on the device (chacha.hpp: the generator shared with the host)
 //   accumulator_stream.hip  powers-of-tau files streamed through the device: wire records in host memory on both sides, bounded pieces
+//   point_diff.hip  out[i] = in[i + shift] - in[i] on affine G1 records: the H bases of prepare_phase2 without index arrays
 //   fixed_base.hip  one base, a window table of its multiples, no doublings per scalar (fixed_base.hpp: the program shared with the host);
 //                   table sets over several G1 bases and linear combinations over them, sliced over lanes (the slice plan)
 //   (msm_g1.hip, msm_g2.hip, msm_partition.hip, ntt.hip, point_fft*.hip, codec.hip, field_ops.hip, records.hip: the kernels behind the functions declared below)
@@ -163,6 +164,18 @@ int accumulator_transform(uint8_t* out, const uint8_t* in, size_t n, uint64_t fi
 template <int GROUP>
 int accumulator_power_pairs(const uint8_t* in, size_t n, int compressed, int checked, int check_subgroup, const uint32_t* key, uint64_t stream_id,
                             uint64_t first, uint8_t* out_uncompressed, size_t piece, uint64_t* out_s, uint64_t* out_sx, long long* err_index);
+// wire records in host memory <-> a whole vector of raw affine records on the device, in pieces (mi355zk_bn254_g{1,2}_points_load / _store)
+template <int GROUP>
+int points_load(void* d_out, const uint8_t* in, size_t n, int compressed, int checked, int check_subgroup, size_t piece, long long* err_index);
+template <int GROUP>
+int points_store(uint8_t* out, const void* d_in, size_t n, int compressed, size_t piece);
+extern template int points_load<1>(void*, const uint8_t*, size_t, int, int, int, size_t, long long*);
+extern template int points_load<2>(void*, const uint8_t*, size_t, int, int, int, size_t, long long*);
+extern template int points_store<1>(uint8_t*, const void*, size_t, int, size_t);
+extern template int points_store<2>(uint8_t*, const void*, size_t, int, size_t);
+// point_diff.hip: out[i] = in[i + shift] - in[i], affine G1 records (the H bases of prepare_phase2); the same lane routine on the host
+int g1_shifted_difference(void* d_out, const void* d_in, size_t n_in, size_t shift, size_t n_out, hipStream_t st);
+int g1_shifted_difference_host(uint64_t* out, const uint64_t* in, size_t n_in, size_t shift, size_t n_out);
 extern template int accumulator_transform<1>(uint8_t*, const uint8_t*, size_t, uint64_t, const uint64_t*, const uint64_t*, int, int, int, uint32_t, size_t, long long*);
 extern template int accumulator_transform<2>(uint8_t*, const uint8_t*, size_t, uint64_t, const uint64_t*, const uint64_t*, int, int, int, uint32_t, size_t, long long*);
 extern template int accumulator_power_pairs<1>(const uint8_t*, size_t, int, int, int, const uint32_t*, uint64_t, uint64_t, uint8_t*, size_t, uint64_t*, uint64_t*, long long*);

@@ -21,6 +21,8 @@ ABI_VERSION = 7   # MI355ZK_ABI_VERSION of the include/mi355zk.h this table was 
 H_INTO_REPR = 1   # MI355ZK_H_INTO_REPR: flags of fr_h_poly[_dev]
 FIXED_SCALARS_MONTGOMERY = 1   # MI355ZK_FIXED_SCALARS_MONTGOMERY: flags of fixed_base_mul_dev
 FIXED_BASES_LANE_TARGET = 262144  # MI355ZK_FIXED_BASES_LANE_TARGET: the lane count mi355zk_fixed_bases_plan aims for
+SHIFTED_DIFFERENCE_K = 16   # MI355ZK_SHIFTED_DIFFERENCE_K: outputs per shared inversion of g1_shifted_difference
+POINTS_PIECE = 1 << 18   # the piece of points_load / points_store (and of the accumulator entry points) when the caller passes 0
 EXP_SAME_SCALAR, FFT_INVERSE, G2_TRUSTED_SUBGROUP = 1, 1, 2   # mode / flag bits of batch_exp, point_fft, sparse_matvec (include/mi355zk.h)
 
 _vp, _sz, _i, _u32 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32
@@ -145,6 +147,12 @@ SIGNATURES = {
     "mi355zk_bn254_g2_accumulator_transform": (_i, [_vp, _vp, _sz, C.c_uint64, _vp, _vp, _i, _i, _i, _u32, _sz, C.POINTER(C.c_longlong)]),
     "mi355zk_bn254_g1_accumulator_power_pairs": (_i, [_vp, _sz, _i, _i, _i, _u32p, C.c_uint64, C.c_uint64, _vp, _sz, _vp, _vp, C.POINTER(C.c_longlong)]),
     "mi355zk_bn254_g2_accumulator_power_pairs": (_i, [_vp, _sz, _i, _i, _i, _u32p, C.c_uint64, C.c_uint64, _vp, _sz, _vp, _vp, C.POINTER(C.c_longlong)]),
+    "mi355zk_bn254_g1_points_load": (_i, [_vp, _vp, _sz, _i, _i, _i, _sz, C.POINTER(C.c_longlong)]),
+    "mi355zk_bn254_g2_points_load": (_i, [_vp, _vp, _sz, _i, _i, _i, _sz, C.POINTER(C.c_longlong)]),
+    "mi355zk_bn254_g1_points_store": (_i, [_vp, _vp, _sz, _i, _sz]),
+    "mi355zk_bn254_g2_points_store": (_i, [_vp, _vp, _sz, _i, _sz]),
+    "mi355zk_bn254_g1_shifted_difference_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _vp]),
+    "mi355zk_selftest_g1_shifted_difference": (_i, [_vp, _vp, _sz, _sz, _sz]),
     "mi355zk_bn254_g2_subgroup_check_dev":(_i, [_vp, _sz, _vp, C.POINTER(C.c_longlong)]),
     "mi355zk_selftest_g2_in_subgroup": (_i, [_vp]),
     "mi355zk_bn254_pairing_product_dev": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp]),

@@ -3,6 +3,8 @@
   powersoftau/src/bin/new_constrained.rs               new_constrained(path, power, batch_size)
   powersoftau/src/bin/compute_constrained.rs           compute_constrained(challenge, response, power, batch_size, ...)
   powersoftau/src/bin/verify_transform_constrained.rs  verify_transform_constrained(challenge, response, new_challenge, power, batch_size, ...)
+  powersoftau/src/bin/prepare_phase2.rs                prepare_phase2_files(response, out_dir, power, degrees, ...) over prepare_phase2_plan;
+                                                       read_phase1radix2m_file reads a result back (the second half of this module)
 
 The reference's only accumulator is BatchedAccumulator over mmap'ed files (batched_accumulator.rs:394-531, 553-600, 1187-1290): a power-28
 challenge is ~103 GB.  verify.contribute_response / read_response / next_challenge hold a whole file in HBM after several whole-file copies on
@@ -284,3 +286,252 @@ def verify_transform_constrained(challenge_path, response_path, new_challenge_pa
         if not ok and os.path.exists(new_challenge_path):
             os.remove(new_challenge_path)
     return response_hash, calculate_hash_file(new_challenge_path)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# prepare_phase2, file to files (powersoftau/src/bin/prepare_phase2.rs): a response (or challenge) -> phase1radix2m{k} for every degree.
+# Whole VECTORS cross the link here, not chunks: a point ifft needs its 2^k inputs together.  mi355zk_bn254_g{1,2}_points_load decodes a
+# vector's prefix from the mapping into one device tensor, in pieces; points_store encodes a device tensor into a mapping.
+
+PlanLoad = collections.namedtuple("PlanLoad", "vector group count offset")       # `count` records from byte `offset` of the input file
+PlanSection = collections.namedtuple("PlanSection", "name group count offset")   # a section of an output file
+PlanFile = collections.namedtuple("PlanFile", "size sections")                   # sections: {name: PlanSection}, in _RADIX_FIELDS' order
+# the Lagrange sections each source vector feeds
+_RADIX_SOURCES = (("tau_g1", "coeffs_g1"), ("tau_g2", "coeffs_g2"), ("alpha_g1", "alpha_coeffs_g1"), ("beta_g1", "beta_coeffs_g1"))
+# bytes per point of a point transform's scratch (working point, Z coordinate, window-table entry) and its lanes per launch, G1 / G2
+_PFFT_SCRATCH = {1: (112, 32, 192, 1 << 20), 2: (224, 64, 368, 1 << 19)}
+
+
+def _al256(x: int) -> int:
+    return (x + 255) & ~255
+
+
+def radix_file_layout(m: int) -> PlanFile:
+    """phase1radix2m{log2 m}: the sections of ceremony._RADIX_FIELDS, uncompressed, back to back: 256 + 320 m + 64 (m - 1) bytes"""
+    off, sections = 0, collections.OrderedDict()
+    for name, g, cnt in ceremony._RADIX_FIELDS:
+        sections[name] = PlanSection(name, g, cnt(m), off)
+        off += cnt(m) * ceremony._ENC_SIZE[(g, False)]
+    return PlanFile(off, sections)
+
+
+class Phase2Plan:
+    """What prepare_phase2_files does, as host arithmetic (prepare_phase2_plan builds it):
+
+      power, compressed, degrees (sorted, distinct), kmax, input_size
+      loads   {vector: PlanLoad} in the order the vectors are loaded: the prefix every degree needs, loaded ONCE
+      files   {k: PlanFile}
+      order   the steps, in order: ("load", vector), ("head", section), ("ifft", vector, k, section), ("h", k), ("free", vector)
+    """
+
+    def __init__(self, power, compressed, degrees, input_size, loads, files, order):
+        self.power, self.compressed, self.degrees, self.kmax, self.input_size = power, compressed, degrees, degrees[-1], input_size
+        self.loads, self.files, self.order = loads, files, order
+
+    def device_bytes(self, piece: int = 0) -> int:
+        """The peak device memory of the flow beyond what the process held before, for pieces of `piece` records (0: lib.POINTS_PIECE).
+        One source vector is resident at a time, with n = 2^kmax and R = 64 / 128 B the raw record of its group:
+
+          the vector          count * R        (count = 2 n - 1 for tau_g1, n otherwise)
+          the work buffer     n * R            (every degree's copy, and then its H bases, are views of this one buffer)
+          point_ifft at n     n * W + (n / 2 + 1) * 32 + n * Z + 8 * min(n, LANES) * T, each term rounded up to 256 B: working points,
+                              twiddles, Z coordinates and the window table (W, Z, T = 112, 32, 192 B and LANES = 2^20 for G1; 224, 64, 368 B
+                              and 2^19 for G2) -- allocated and freed by every transform, largest at kmax
+                              + n B for a G2 transform's membership flags (counted always: check_g2_subgroup=False runs the test per call)
+
+        and the maximum over the vectors is taken (G2 at equal n: 256 n against G1's 192 n - 64).  Next to it the ONE pooled buffer of
+        points_load / points_store, which is leased by one call at a time and grows to the largest request: with P = min(piece, count)
+
+          load    2 * (P * in_record + P [G2] + 256)        store   2 * P * R
+
+        (include/mi355zk.h), the maximum over all calls.  The shifted difference allocates nothing.  torch's allocator is asked to return
+        its cached blocks after every vector, so what one vector held is not still held under the next.  On top of the resident sum goes
+        1 / 32 of it for what the allocators and the runtime add (rounding of every allocation, page tables): an allowance, not a
+        derivation -- the low-water mark of free device memory lay 1.7 % above the sum at 2^20 and 0.6 % at 2^18 (profiles/prepare_phase2.md).
+        One-time costs of the process (code objects, streams) are not counted."""
+        piece = piece or _lib.POINTS_PIECE
+        n = 1 << self.kmax
+        peak = lease = 0
+        for ld in self.loads.values():
+            rec = 64 * ld.group
+            in_rec = ceremony._ENC_SIZE[(ld.group, self.compressed)]
+            p = min(piece, ld.count)
+            lease = max(lease, 2 * (_al256(p * in_rec) + (_al256(p) if ld.group == 2 else 0) + 256))
+            held = ld.count * rec
+            if ld.vector != "beta_g2":
+                w, z, t, lanes = _PFFT_SCRATCH[ld.group]
+                held += n * rec + _al256(n * w) + _al256((n // 2 + 1) * 32) + _al256(n * z) + 8 * min(n, lanes) * t + (n if ld.group == 2 else 0)
+                lease = max(lease, 2 * _al256(min(piece, n) * rec))
+            peak = max(peak, held)
+        return peak + peak // 32 + lease
+
+
+def prepare_phase2_plan(power: int, degrees=None, compressed: bool = True) -> Phase2Plan:
+    """The plan of prepare_phase2_files for an accumulator file of `power`.  degrees: the exponents k of the files phase1radix2m{k} to
+    write; None: every k in 0 .. power, the reference's loop (prepare_phase2.rs:60).  0 <= k <= power, duplicates collapse; anything else
+    raises ValueError.  Every source vector is loaded once, as the prefix the LARGEST degree needs -- 2^kmax records, 2^(kmax + 1) - 1 of
+    tau_g1 (the H bases reach m - 1 places past m) -- and every smaller degree works on a prefix of that."""
+    if isinstance(power, bool) or not isinstance(power, int) or not 0 <= power <= 28:
+        raise ValueError("prepare_phase2_plan: 0 <= power <= 28")
+    if degrees is None:
+        degrees = range(power + 1)
+    degrees = list(degrees)
+    if not degrees or any(isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k <= power for k in degrees):
+        raise ValueError(f"prepare_phase2_plan: degrees are exponents k with 0 <= k <= {power}, at least one")
+    degrees = tuple(sorted({int(k) for k in degrees}))
+    kmax = degrees[-1]
+    layout, body = ceremony.accumulator_layout(power, compressed)
+    lay = {name: (g, cnt, off) for name, g, cnt, off in layout}
+    want = {"tau_g1": (2 << kmax) - 1, "tau_g2": 1 << kmax, "alpha_g1": 1 << kmax, "beta_g1": 1 << kmax, "beta_g2": 1}
+    loads = collections.OrderedDict((name, PlanLoad(name, lay[name][0], min(want[name], lay[name][1]), lay[name][2])) for name, _, _ in ceremony._ACC_FIELDS)
+    files = collections.OrderedDict((k, radix_file_layout(1 << k)) for k in degrees)
+    order = []
+    for vector, section in _RADIX_SOURCES:
+        order.append(("load", vector))
+        if vector in ("alpha_g1", "beta_g1"):
+            order.append(("head", vector))
+        order += [("ifft", vector, k, section) for k in degrees]
+        if vector == "tau_g1":
+            order += [("h", k) for k in degrees if k > 0]
+        order.append(("free", vector))
+    order += [("load", "beta_g2"), ("head", "beta_g2"), ("free", "beta_g2")]
+    return Phase2Plan(power, bool(compressed), degrees, body + (keys.PUBLIC_KEY_SIZE if compressed else 0), loads, files, order)
+
+
+def _raise_points(rc: int, index: int, vector: str, what: str):
+    """the stream module's exception for a non-zero return of points_load / points_store"""
+    _raise_for(rc, index, Batch(vector, 0, 0, 0, 0, 0, 0), what)
+
+
+def points_load(data: np.ndarray, group: int, count: int, compressed: bool, checked: bool = True, check_subgroup: bool = False, piece: int = 0,
+                vector: str = "points"):
+    """`count` wire records at the start of `data` (a contiguous uint8 host array, typically a slice of a mapping) -> a (count, 8 * group)
+    int64 tensor of raw affine records on the current device: mi355zk_bn254_g{1,2}_points_load.  The current stream is synchronised first;
+    the call returns when the tensor is complete.  Raises GroupDecodingError(kind, index), DeserializationError("PointAtInfinity in
+    <vector>") or VerificationError("g2 subgroup") for the first piece that fails."""
+    import torch
+
+    size = ceremony._ENC_SIZE[(group, bool(compressed))]
+    if data.dtype != np.uint8 or not data.flags["C_CONTIGUOUS"] or data.size < count * size:
+        raise ValueError(f"points_load: {vector} needs {count * size} contiguous bytes")
+    out = torch.empty((count, 8 * group), dtype=torch.int64, device=torch.device("cuda", torch.cuda.current_device()))
+    torch.cuda.current_stream().synchronize()
+    idx = C.c_longlong(-1)
+    rc = getattr(_lib.load(), f"mi355zk_bn254_g{group}_points_load")(
+        C.c_void_p(out.data_ptr()), C.c_void_p(data.ctypes.data), count, 1 if compressed else 0, 1 if checked else 0, 1 if check_subgroup else 0,
+        piece, C.byref(idx))
+    if rc:
+        _raise_points(rc, idx.value, vector, "points_load")
+    return out
+
+
+def points_store(data: np.ndarray, points, compressed: bool, piece: int = 0):
+    """The inverse: the (n, 8) / (n, 16) device records `points` encoded into the start of `data` (a writable contiguous uint8 host array):
+    mi355zk_bn254_g{1,2}_points_store.  The current stream is synchronised first; the call returns when the bytes are in `data`."""
+    import torch
+
+    group = ceremony._group(points)
+    n = points.shape[0]
+    size = ceremony._ENC_SIZE[(group, bool(compressed))]
+    if data.dtype != np.uint8 or not data.flags["C_CONTIGUOUS"] or not data.flags["WRITEABLE"] or data.size < n * size or not points.is_contiguous():
+        raise ValueError(f"points_store: {n * size} writable contiguous bytes and contiguous records")
+    torch.cuda.current_stream().synchronize()
+    rc = getattr(_lib.load(), f"mi355zk_bn254_g{group}_points_store")(C.c_void_p(data.ctypes.data), C.c_void_p(points.data_ptr()), n,
+                                                                    1 if compressed else 0, piece)
+    if rc:
+        _raise_points(rc, -1, "points", "points_store")
+
+
+def prepare_phase2_files(path, out_dir, power: int, degrees=None, compressed: bool = True, checked: bool = True, check_g2_subgroup: bool = True,
+                         piece: int = 0):
+    """prepare_phase2.rs, file to files: the accumulator in `path` -> out_dir/phase1radix2m{k} for every k of `degrees` (None: 0 .. power, the
+    reference's loop); returns {k: path}.  Each file is byte for byte ceremony.write_phase1radix2m(ceremony.prepare_phase2(acc, 2^k)).
+
+    compressed=True: `path` is a response (compressed body + public key, response_size(power) bytes -- what the reference reads, with
+    CheckForCorrectness::Yes = `checked`); False: a challenge (challenge_size(power)).  Another size raises ValueError.  The input is mapped,
+    never read whole; the outputs are created at their final size (an existing one raises FileExistsError before any work: the reference's
+    create_new) and mapped; every file this call created is removed when it fails.
+
+    The work is vector-major (prepare_phase2_plan(...).order): each of tau_g1, tau_g2, alpha_g1, beta_g1 is uploaded and decoded ONCE, as the
+    prefix the largest degree needs; then for every k its first 2^k records are copied, transformed (ceremony.point_ifft) and stored into
+    that file's section -- for tau_g1 also the H bases tau_g1[i + 2^k] - tau_g1[i] (ceremony.shifted_difference) -- and the vector is
+    freed.  alpha_g1[0], beta_g1[0] and beta_g2 head every file.  One vector is on the device at a time: Phase2Plan.device_bytes(piece).
+    check_g2_subgroup: tau_g2 and beta_g2 are tested for membership at load (VerificationError("g2 subgroup")) and the G2 transforms run as
+    trusted; False: no test at load, and point_ifft runs its own per call.  Only the prefixes that are loaded are decoded and checked: with
+    degrees below `power` the rest of the file is not looked at.
+    Raises GroupDecodingError(kind, index in the vector), DeserializationError("PointAtInfinity in <vector>"), VerificationError."""
+    import torch
+
+    plan = prepare_phase2_plan(power, degrees, compressed)
+    _check_size(path, plan.input_size, "response" if compressed else "challenge")
+    os.makedirs(out_dir, exist_ok=True)
+    paths = collections.OrderedDict((k, os.path.join(out_dir, f"phase1radix2m{k}")) for k in plan.degrees)
+    for p in paths.values():
+        if os.path.lexists(p):
+            raise FileExistsError(p)
+    src = np.memmap(path, dtype=np.uint8, mode="r")
+    outs, created = {}, []
+    ok = False
+    try:
+        for k, p in paths.items():
+            with open(p, "xb") as f:
+                f.truncate(plan.files[k].size)
+            created.append(p)
+            outs[k] = np.memmap(p, dtype=np.uint8, mode="r+")
+
+        def section(k, name):
+            s = plan.files[k].sections[name]
+            return outs[k][s.offset:s.offset + s.count * ceremony._ENC_SIZE[(s.group, False)]]
+
+        vec = work = copy = None
+        for step in plan.order:
+            if step[0] == "load":
+                ld = plan.loads[step[1]]
+                in_size = ceremony._ENC_SIZE[(ld.group, plan.compressed)]
+                vec = points_load(src[ld.offset:ld.offset + ld.count * in_size], ld.group, ld.count, plan.compressed, checked,
+                                  check_g2_subgroup and ld.group == 2, piece, ld.vector)
+                if ld.vector != "beta_g2":
+                    work = torch.empty((1 << plan.kmax, 8 * ld.group), dtype=torch.int64, device=vec.device)
+            elif step[0] == "head":
+                for k in plan.degrees:
+                    points_store(section(k, step[1]), vec[:1], False, piece)
+            elif step[0] == "ifft":
+                _, _, k, name = step
+                copy = work[:1 << k]
+                copy.copy_(vec[:1 << k])
+                ceremony.point_ifft(copy, trusted_subgroup=bool(check_g2_subgroup))
+                points_store(section(k, name), copy, False, piece)
+            elif step[0] == "h":
+                m = 1 << step[1]
+                points_store(section(step[1], "h"), ceremony.shifted_difference(vec, m, m - 1, out=work), False, piece)
+            else:   # "free" (the views too: one of them would keep the work buffer alive under the next vector)
+                vec = work = copy = None
+                torch.cuda.empty_cache()
+        for o in outs.values():
+            o.flush()
+        ok = True
+    finally:
+        del src
+        outs.clear()
+        if not ok:
+            for p in created:
+                if os.path.exists(p):
+                    os.remove(p)
+    return dict(paths)
+
+
+def read_phase1radix2m_file(path, m: int):
+    """A phase1radix2m{log2 m} file -> the dict of raw affine device records ceremony.read_phase1radix2m gives for its bytes
+    (phase2/src/parameters.rs:147-217: into_affine_unchecked, the point at infinity refused -> DeserializationError), loaded section by
+    section from the mapping with points_load: no whole-file tensor, so circom.mpc_parameters_new can start from a file of any degree.
+    ValueError when m is no power of two or the file's size is not that of degree m."""
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or m < 1 or m & (m - 1):
+        raise ValueError("read_phase1radix2m_file: m must be a power of two")
+    lay = radix_file_layout(int(m))
+    _check_size(path, lay.size, "phase1radix2m")
+    src = np.memmap(path, dtype=np.uint8, mode="r")
+    try:
+        return {s.name: points_load(src[s.offset:s.offset + s.count * ceremony._ENC_SIZE[(s.group, False)]], s.group, s.count, False, False, False,
+                                    0, s.name) for s in lay.sections.values()}
+    finally:
+        del src
