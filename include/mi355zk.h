@@ -383,6 +383,13 @@ int mi355zk_selftest_u_reduce32(int which, const uint32_t in_u[9], uint64_t out_
 int mi355zk_selftest_g1_accumulate(int mode, const uint64_t *affine_pts, const uint8_t *negate, size_t n, uint64_t out_xyzz[16]);
 int mi355zk_selftest_g1_record_sum(int mode, const uint64_t *affine_pts, const uint8_t *negate, const uint32_t *group, size_t n, size_t n_groups, uint64_t out_xyzz[16]);
 int mi355zk_selftest_g2_record_sum(int mode, const uint64_t *affine_pts, const uint8_t *negate, const uint32_t *group, size_t n, size_t n_groups, uint64_t out_xyzz[32]);
+/* The dense G1 multiexp over device buffers (as mi355zk_bn254_g1_dense_multiexp_dev; one chunk) that ALSO hands back what its accumulate stage left,
+ * before the bucket reduction: first[b] / last[b], the bounds of bucket b's index list in vals (entries: base index, bit 31 = negate, in the order the
+ * lane adds them), and the bucket array (records: 16 u64 per bucket -- X, Y, ZZ, ZZZ canonical, 2^261 domain; all zero: empty or infinity).
+ * *n_buckets and *n_vals are always set; a capacity below them returns 3 with nothing copied. */
+int mi355zk_selftest_g1_msm_buckets_dev(const void *d_bases, const void *d_scalars, size_t n, void *stream, uint64_t out_xyz[12], uint32_t *n_buckets,
+                                        uint32_t *n_vals, uint32_t *first, uint32_t *last, size_t cap_buckets, uint32_t *vals, size_t cap_vals,
+                                        uint64_t *records);
 int mi355zk_selftest_msm_digits(size_t n_scalars, uint32_t window_groups, const uint32_t scalar[8], uint32_t w_start, uint32_t w_stop, int direct, int32_t *digits, uint32_t *geom);
 int mi355zk_selftest_glv_split(const uint32_t k[8], uint32_t out[12]);
 int mi355zk_selftest_glv_wnaf5(const uint32_t m[5], int8_t digits[164]);

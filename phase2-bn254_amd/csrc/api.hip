@@ -504,6 +504,14 @@ int mi355zk_bn254_g1_dense_multiexp_dev(const void* d_bases, const void* d_scala
     return msm_g1_dense_device(d_bases, nullptr, d_scalars, n, (hipStream_t)stream, out_xyz, nullptr);
   });
 }
+int mi355zk_selftest_g1_msm_buckets_dev(const void* d_bases, const void* d_scalars, size_t n, void* stream, uint64_t out_xyz[12], uint32_t* n_buckets,
+                                        uint32_t* n_vals, uint32_t* first, uint32_t* last, size_t cap_buckets, uint32_t* vals, size_t cap_vals,
+                                        uint64_t* records) {
+  return abi_guard([&]() -> int {
+    if (!out_xyz || !n_buckets || !n_vals || !first || !last || !vals || !records || !n || !d_bases || !d_scalars || n >= (1ull << 31)) return ZK_ERR_BAD_ARGS;
+    return msm_g1_buckets_device(d_bases, d_scalars, n, (hipStream_t)stream, out_xyz, n_buckets, n_vals, first, last, cap_buckets, vals, cap_vals, records);
+  });
+}
 int mi355zk_bn254_g2_dense_multiexp_dev(const void* d_bases, const void* d_scalars, size_t n, void* stream, uint64_t out_xyz[24]) {
   return abi_guard([&]() -> int {
     if (!out_xyz || (n && (!d_bases || !d_scalars)) || n >= (1ull << 31)) return ZK_ERR_BAD_ARGS;

@@ -40,6 +40,8 @@ int msm_g2_device(const void* d_bases, uint64_t n_bases, uint64_t base_offset, c
                   const uint32_t* d_dprefix, hipStream_t st, uint64_t out_xyz[24], long long* err_index, uint32_t wgroups, uint32_t wgroup, bool scalars_mont,
                   MsmChunks* chunks, uint64_t table_stride = 0, uint32_t table_c = 0);
 int msm_g1_dense_device(const void* d_bases, const void* d_bases2, const void* d_scalars, uint64_t n, hipStream_t st, uint64_t* out_xyz, uint64_t* out2_xyz);
+int msm_g1_buckets_device(const void* d_bases, const void* d_scalars, uint64_t n, hipStream_t st, uint64_t out_xyz[12], uint32_t* n_buckets, uint32_t* n_vals,
+                          uint32_t* first, uint32_t* last, size_t cap_buckets, uint32_t* vals, size_t cap_vals, uint64_t* records);
 int msm_g2_dense_device(const void* d_bases, const void* d_bases2, const void* d_scalars, uint64_t n, hipStream_t st, uint64_t* out_xyz, uint64_t* out2_xyz);
 int segsum_g1_device(const void* d_points, uint64_t nnz, const uint32_t* d_row_ptr, uint32_t n_rows, hipStream_t st, void* d_out);
 int segsum_g2_device(const void* d_points, uint64_t nnz, const uint32_t* d_row_ptr, uint32_t n_rows, hipStream_t st, void* d_out);

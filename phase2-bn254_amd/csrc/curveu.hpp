@@ -15,6 +15,8 @@
 //     by which a product of two values (in units of p) shrinks:  u_mul(a, b) < (a/p)(b/p) * 0.006 p + p.
 //     Accumulator invariant:  X < 6p,  Y < 2p,  ZZ < 2p,  ZZZ < 2p,  all N-form.
 //     Infinity is ZZ == literal zero limbs.
+//     tests/cpp/test_u_bounds_host.cpp runs these very lines on limbs that carry worst-case intervals and fails if a column sum can
+//     pass 2^64, a limb expression can wrap, or a stated precondition is not met by what a caller passes.
 #pragma once
 
 #include "curve.hpp"
@@ -35,7 +37,7 @@ ZK_HD bool u_is_zero_lt8p(const FpU<PR>& a) {
   bool z = a.limbs_all_zero();
   for_limbs<7>([&](auto kc) {
     constexpr int k = decltype(kc)::value + 1;
-    uint32_t e = 0;
+    ulimb_t e = 0;
     for_limbs<9>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
       constexpr uint32_t c = USubConst<PR, k, 0>::limb(i);  // k*p on normalised limbs
@@ -90,42 +92,49 @@ ZK_HD XYZZU<PR> xyzzu_double(const XYZZU<PR>& a) {
   return r;
 }
 
-// acc += (+/-)(x2, y2);  (x2, y2) != infinity, canonical memory-format coordinates.
+// the signed y of a loaded point: y or p - y, in (0, p], N-form (the rare paths only: a bucket's first point, the doubling)
 template <class PR>
-ZK_HD void xyzzu_add_mixed(XYZZU<PR>& acc, const Fp<PR>& x2s, const Fp<PR>& y2s, bool negate) {
-  const FpU<PR> x2 = u_from_std(x2s);                      // < p, N
-  FpU<PR> y2 = u_from_std(y2s);                            // < p, N
-  {
-    FpU<PR> ny = u_sub<1, 1>(FpU<PR>::zero(), y2);          // p - y2 in (0, p], N
+ZK_HD FpU<PR> u_signed_y(const FpU<PR>& y, bool negate) {
+  const FpU<PR> ny = u_sub<1, 1>(FpU<PR>::zero(), y);        // p - y in (0, p], N
+  FpU<PR> r;
 #pragma unroll
-    for (int i = 0; i < 9; ++i) y2.l[i] = negate ? ny.l[i] : y2.l[i];
-  }
+  for (int i = 0; i < 9; ++i) r.l[i] = negate ? ny.l[i] : y.l[i];
+  UChk::either(r, ny, y);
+  return r;
+}
+
+// acc += (+/-)(x2, y2);  (x2, y2) != infinity, canonical coordinates of the memory format re-packed (u_from_std: < p, N-form).
+// The sign never touches y2: S2 = y2 * ZZZ1 is formed with the stored y2 and enters R = (+/-) S2 - Y1 with its sign, limb by limb, in
+// the sum that is carried anyway (u_sub_signed).
+template <class PR>
+ZK_HD void xyzzu_add_mixed_u(XYZZU<PR>& acc, const FpU<PR>& x2, const FpU<PR>& y2, bool negate) {
   if (acc.is_zero()) {
     const FpU<PR> C = UPow2<PR, 266>::get();
     acc.x = u_mul(x2, C);                                   // x * 2^261 < 2p
-    acc.y = u_mul(y2, C);
+    acc.y = u_mul(u_signed_y(y2, negate), C);
     acc.zz = C;                                             // 1 * 2^266
     acc.zzz = C;
     return;
   }
   FpU<PR> u2 = u_mul(x2, acc.zz);                           // < 2p
-  FpU<PR> s2 = u_mul(y2, acc.zzz);                          // < 2p
+  FpU<PR> s2 = u_mul(y2, acc.zzz);                          // 2c + 1 < 1.02p, N  (the UNSIGNED y2)
   FpU<PR> p = u_sub<8, 1>(u2, acc.x);                       // X < 6p <= 8p;   P < 10p, N
-  FpU<PR> r = u_sub<2, 1>(s2, acc.y);                       // Y < 2p;         R < 4p, N
+  FpU<PR> r = u_sub_signed<4>(s2, negate, acc.y);           // 4p +/- S2 - Y1:  S2 + Y1 < 4p;   R < 5.02p, N
   FpU<PR> pp = u_sqr(p);                                    // 100c + 1 < 1.6p
   FpU<PR> ppp = u_mul(p, pp);                               // < 1.1p
   FpU<PR> q = u_mul(acc.x, pp);                             // < 1.06p
-  FpU<PR> rr = u_sqr(r);                                    // 16c + 1 < 1.1p
+  FpU<PR> rr = u_sqr(r);                                    // 25.2c + 1 < 1.16p
   FpU<PR> t = u_add(ppp, u_dbl(q));                         // < 3.3p <= 4p, limbs < 3 * 2^29
-  FpU<PR> x3 = u_sub<4, 3>(rr, t);                          // < 5.1p  (invariant X < 6p)
-  FpU<PR> d = u_sub<8, 1>(q, x3);                           // < 9.1p
+  FpU<PR> x3 = u_sub<4, 3>(rr, t);                          // < 5.16p  (invariant X < 6p)
+  FpU<PR> d = u_sub_lazy<8, 1>(q, x3);                      // < 9.06p;  NOT carried (it only feeds the product below): limbs < 3 * 2^29, top limb >= (2.8p >> 232) - 1
   FpU<PR> ny1 = u_sub<2, 1>(FpU<PR>::zero(), acc.y);        // 2p - Y1 in (0, 2p], N
-  FpU<PR> y3 = u_mul2(r, d, ny1, ppp);                      // R*D - Y1*PPP: (4*9.1 + 2*1.1) c + 1 < 1.24p  (invariant Y < 2p)
+  FpU<PR> y3 = u_mul2(r, d, ny1, ppp);                      // R*D - Y1*PPP: (5.02*9.06 + 2*1.1) c + 1 < 1.29p  (invariant Y < 2p);  limb products (3 + 1) * 2^58
   FpU<PR> zz3 = u_mul(acc.zz, pp);                          // < 2p
   FpU<PR> zzz3 = u_mul(acc.zzz, ppp);                       // < 2p
   if (u_is_zero_lt2p(zz3)) {
     // P == 0 (ZZ1 != 0): the points have the same x.  Same point -> double (ec.rs:483-485); opposite -> infinity (ec.rs:487).
-    if (u_is_zero_lt8p(r)) acc = xyzzu_double_affine(x2, y2);
+    // R == 0 mod p is read off R itself whatever the sign: (+/-) S2 == Y1.
+    if (u_is_zero_lt8p(r)) acc = xyzzu_double_affine(x2, u_signed_y(y2, negate));
     else acc = XYZZU<PR>::zero();
     return;
   }
@@ -133,6 +142,10 @@ ZK_HD void xyzzu_add_mixed(XYZZU<PR>& acc, const Fp<PR>& x2s, const Fp<PR>& y2s,
   acc.y = y3;
   acc.zz = zz3;
   acc.zzz = zzz3;
+}
+template <class PR>
+ZK_HD void xyzzu_add_mixed(XYZZU<PR>& acc, const Fp<PR>& x2s, const Fp<PR>& y2s, bool negate) {
+  xyzzu_add_mixed_u(acc, u_from_std(x2s), u_from_std(y2s), negate);
 }
 
 // 32 * a for an N-form a < 2p, N-form again: a 5-bit shift across the 29-bit limbs (l[8] < 2^23 going in, < 2^28 coming out)
@@ -143,6 +156,7 @@ ZK_HD FpU<PR> u_shl5_lt2p(const FpU<PR>& a) {
 #pragma unroll
   for (int i = 1; i < 8; ++i) r.l[i] = ((a.l[i] << 5) & U_MASK) | (a.l[i - 1] >> 24);
   r.l[8] = (a.l[8] << 5) | (a.l[7] >> 24);
+  UChk::times<32>(r, a);
   return r;
 }
 
@@ -161,10 +175,10 @@ ZK_HD FpU<PR> u_shl5_lt2p(const FpU<PR>& a) {
 // Result under the accumulator invariant: X < 6p, Y < 2p, ZZ < 2p, ZZZ < 2p, N-form; infinity is literal-zero ZZ.
 // Equal x (equal memory words: the coordinates are canonical): the same signed y doubles (xyzzu_double_affine, as xyzzu_add_mixed does),
 // anything else is the opposite point: infinity.
+// (the _u form takes the coordinates re-packed, < p and N-form, and whether the two x are equal: what the bound checker instantiates)
 template <class PR>
-ZK_HD XYZZU<PR> xyzzu_from_affine_pair(const Fp<PR>& x1s, const Fp<PR>& y1s, bool neg1, const Fp<PR>& x2s, const Fp<PR>& y2s, bool neg2) {
-  const FpU<PR> x1 = u_from_std(x1s), x2 = u_from_std(x2s);     // < p, N
-  FpU<PR> y1 = u_from_std(y1s), y2 = u_from_std(y2s);           // < p, N
+ZK_HD XYZZU<PR> xyzzu_from_affine_pair_u(const FpU<PR>& x1, const FpU<PR>& y1u, bool neg1, const FpU<PR>& x2, const FpU<PR>& y2u, bool neg2, bool same_x) {
+  FpU<PR> y1 = y1u, y2 = y2u;
   {
     const FpU<PR> n1 = u_sub<1, 1>(FpU<PR>::zero(), y1);         // p - y1 in (0, p], N
     const FpU<PR> n2 = u_sub<1, 1>(FpU<PR>::zero(), y2);
@@ -173,14 +187,16 @@ ZK_HD XYZZU<PR> xyzzu_from_affine_pair(const Fp<PR>& x1s, const Fp<PR>& y1s, boo
       y1.l[i] = neg1 ? n1.l[i] : y1.l[i];                       // signed y in (0, p): y != 0
       y2.l[i] = neg2 ? n2.l[i] : y2.l[i];
     }
+    UChk::either(y1, n1, y1u);
+    UChk::either(y2, n2, y2u);
   }
   XYZZU<PR> res = XYZZU<PR>::zero();                            // (ONE exit: see xyzzr_add_quad)
-  if (x1s == x2s) {
+  if (same_x) {
     // P == 0: same point -> double (ec.rs:483-485); opposite -> infinity (ec.rs:487).  Canonical coordinates (the precondition: see
     // accumulate_run in msm_impl.hpp): equal values are equal words, and equal limbs.  (The test is on the loaded words on purpose: on
     // P or on ZZ == 0 mod p, as xyzzu_add_mixed has it, the rare branch holds more state across the branch and msm_accumulate_kernel
     // goes from 125 to 136 VGPRs -- the fourth wave.)
-    uint32_t d = 0;
+    ulimb_t d = 0;
 #pragma unroll
     for (int i = 0; i < 9; ++i) d |= y1.l[i] ^ y2.l[i];
     if (d == 0) res = xyzzu_double_affine(x2, y2);
@@ -194,13 +210,17 @@ ZK_HD XYZZU<PR> xyzzu_from_affine_pair(const Fp<PR>& x1s, const Fp<PR>& y1s, boo
     const FpU<PR> rr = u_sqr(r);                                // 4c + 1 < 1.03p
     const FpU<PR> t = u_add(zzz, u_dbl(q));                     // < 3.07p <= 4p, limbs < 3 * 2^29
     res.x = u_sub<4, 3>(rr, t);                                 // < 5.03p  (invariant X < 6p)
-    const FpU<PR> d = u_sub<8, 1>(q, res.x);                    // < 9.02p, N
+    const FpU<PR> d = u_sub_lazy<8, 1>(q, res.x);               // < 9.02p;  NOT carried: limbs < 3 * 2^29, top limb >= (2.9p >> 232) - 1
     const FpU<PR> ny1 = u_sub<1, 1>(FpU<PR>::zero(), y1);       // p - y1 in (0, p], N
-    res.y = u_mul2(r, d, ny1, zzz);                             // R*D - y1*PPP: (2 * 9.02 + 1.03) c + 1 < 1.12p  (invariant Y < 2p)
+    res.y = u_mul2(r, d, ny1, zzz);                             // R*D - y1*PPP: (2 * 9.02 + 1.03) c + 1 < 1.12p  (invariant Y < 2p);  limb products (3 + 1) * 2^58
     res.zz = zz;                                                // P != 0 mod p, so ZZ != 0 mod p: never the zero limbs of infinity
     res.zzz = zzz;
   }
   return res;
+}
+template <class PR>
+ZK_HD XYZZU<PR> xyzzu_from_affine_pair(const Fp<PR>& x1s, const Fp<PR>& y1s, bool neg1, const Fp<PR>& x2s, const Fp<PR>& y2s, bool neg2) {
+  return xyzzu_from_affine_pair_u(u_from_std(x1s), u_from_std(y1s), neg1, u_from_std(x2s), u_from_std(y2s), neg2, x1s == x2s);
 }
 
 // accumulator -> memory-format XYZZ (canonical coordinates, 2^256 domain); infinity -> all zero
@@ -298,9 +318,9 @@ ZK_HD void xyzzr_add(XYZZU<PR>& acc, const XYZZU<PR>& o) {
   FpU<PR> rr = u_sqr(r);                                    // < 1.1p
   FpU<PR> t = u_add(ppp, u_dbl(q));                         // < 3.1p <= 4p, limbs < 3 * 2^29
   FpU<PR> x3 = u_sub<4, 3>(rr, t);                          // < 5.1p  (invariant X < 6p)
-  FpU<PR> d = u_sub<8, 1>(q, x3);                           // < 9.1p
+  FpU<PR> d = u_sub_lazy<8, 1>(q, x3);                      // < 9.1p;  NOT carried: limbs < 3 * 2^29, top limb >= (2.9p >> 232) - 1
   FpU<PR> ns1 = u_sub<2, 1>(FpU<PR>::zero(), s1);           // 2p - S1 in (0, 2p], N
-  FpU<PR> y3 = u_mul2(r, d, ns1, ppp);                      // R*D - S1*PPP: (4*9.1 + 2*1.03) c + 1 < 1.24p  (invariant Y < 2p)
+  FpU<PR> y3 = u_mul2(r, d, ns1, ppp);                      // R*D - S1*PPP: (4*9.1 + 2*1.03) c + 1 < 1.24p  (invariant Y < 2p);  limb products (3 + 1) * 2^58
   FpU<PR> zz3 = u_mul(u_mul(acc.zz, o.zz), pp);             // < 2p
   FpU<PR> zzz3 = u_mul(u_mul(acc.zzz, o.zzz), ppp);         // < 2p
   if (u_is_zero_lt2p(zz3)) {

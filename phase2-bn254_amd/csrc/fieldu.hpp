@@ -38,6 +38,35 @@ ZK_HD void for_limbs(F&& f) {
   for_limbs_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
 }
 
+// ---- limb and accumulator types, and the bound hooks ----
+// The product computes on ulimb_t = uint32_t limbs and uacc_t = uint64_t column sums, and every UChk hook below is an empty function.
+// The host bound checker (tests/cpp/u_interval.hpp, tests/cpp/test_u_bounds_host.cpp) defines ZK_U_BOUNDS_CHECK and supplies the three
+// names itself: limbs and sums that carry their value together with a worst-case integer interval, a value bound "< k p" per element
+// (UValueBound, the base of FpU), and hooks that TEST the preconditions stated at the functions below with what the callers pass and
+// NOTE the stated results.  The lines that run are these: the checker instantiates the templates of this file and of curveu.hpp.
+#ifndef ZK_U_BOUNDS_CHECK
+using ulimb_t = uint32_t;
+using uacc_t = uint64_t;
+struct UValueBound {};
+struct UChk {
+  template <class... T> ZK_HD static void zero(T&&...) {}           // r = 0
+  template <class... T> ZK_HD static void canonical(T&&...) {}      // r < p, N-form (a constant)
+  template <class... T> ZK_HD static void copy(T&&...) {}           // value(r) = value(a)
+  template <class... T> ZK_HD static void sum(T&&...) {}            // value(r) = value(a) + value(b)
+  template <class... T> ZK_HD static void either(T&&...) {}         // r is a or b
+  template <int N, class... T> ZK_HD static void times(T&&...) {}   // value(r) = N value(a)
+  template <class... T> ZK_HD static void mul_pre(T&&...) {}        // u_mul's precondition on (a, b)
+  template <class... T> ZK_HD static void sqr_pre(T&&...) {}        // u_sqr's precondition on a
+  template <class... T> ZK_HD static void mul2_pre(T&&...) {}       // u_mul2's precondition on (a, b, c, d)
+  template <class... T> ZK_HD static void mul(T&&...) {}            // r = the Montgomery result of a b (+ c d): value and top limb
+  template <int K, int S, class... T> ZK_HD static void sub_pre(T&&...) {}    // u_sub's preconditions on (a, b)
+  template <int K, class... T> ZK_HD static void sub_signed_pre(T&&...) {}    // u_sub_signed's preconditions on (a, b)
+  template <int K, class... T> ZK_HD static void sub_lazy(T&&...) {}          // value(r) <= value(a) + K p, limbs as computed
+  template <class... T> ZK_HD static void carried_nonneg(T&&...) {}           // r N-form with value(r) >= 0: the top limb is exact again
+  template <int K, class... T> ZK_HD static void require_lt(T&&...) {}        // N-form and value < K p (the u_to_std_* preconditions)
+};
+#endif
+
 constexpr uint32_t U_BITS = 29;
 constexpr uint32_t U_MASK = (1u << U_BITS) - 1u;
 
@@ -59,17 +88,18 @@ struct UParams {
 };
 
 template <class PR>
-struct FpU {
-  uint32_t l[9];
+struct FpU : UValueBound {
+  ulimb_t l[9];
   ZK_HD static FpU zero() {
     FpU r;
 #pragma unroll
     for (int i = 0; i < 9; ++i) r.l[i] = 0;
+    UChk::zero(r);
     return r;
   }
   // exact zero limbs (used for the infinity marker ZZ == 0, which is stored as literal zeros)
   ZK_HD bool limbs_all_zero() const {
-    uint32_t o = 0;
+    ulimb_t o = 0;
 #pragma unroll
     for (int i = 0; i < 9; ++i) o |= l[i];
     return o == 0;
@@ -94,33 +124,34 @@ ZK_HD FpU<PR> u_from_std(const Fp<PR>& a) {
 template <class PR>
 ZK_HD FpU<PR> u_carry(const FpU<PR>& a) {
   FpU<PR> r;
-  uint32_t c = 0;
+  ulimb_t c = 0;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
-    uint32_t t = a.l[i] + c;
+    ulimb_t t = a.l[i] + c;
     r.l[i] = t & U_MASK;
     c = t >> U_BITS;
   }
   r.l[8] = a.l[8] + c;
+  UChk::copy(r, a);
   return r;
 }
 
 // N-form value < 2p  ->  canonical [0, p) in the 8 x 32 memory format
 template <class PR>
-ZK_HD Fp<PR> u_to_std_lt2p(const FpU<PR>& a) {
+ZK_HD Fp<PR> u_words_lt2p_to_std(const uint32_t al[9]) {   // on plain words: the borrow test wraps on purpose
   // d = a - p with borrow propagation on 29-bit limbs
   uint32_t d[9];
   uint32_t borrow = 0;
   for_limbs<9>([&](auto ic) {
     constexpr int i = decltype(ic)::value;
     constexpr uint32_t pi = UParams<PR>::P(i);
-    uint32_t t = a.l[i] - pi - borrow;
+    uint32_t t = al[i] - pi - borrow;
     borrow = t >> 31;  // limbs < 2^30: a wrapped difference has its top bit set
     d[i] = (i < 8) ? (t & U_MASK) : t;
   });
   uint32_t v[9];
 #pragma unroll
-  for (int i = 0; i < 9; ++i) v[i] = borrow ? a.l[i] : d[i];
+  for (int i = 0; i < 9; ++i) v[i] = borrow ? al[i] : d[i];
   Fp<PR> r;
 #pragma unroll
   for (int w = 0; w < 8; ++w) {
@@ -134,6 +165,14 @@ ZK_HD Fp<PR> u_to_std_lt2p(const FpU<PR>& a) {
   }
   return r;
 }
+template <class PR>
+ZK_HD Fp<PR> u_to_std_lt2p(const FpU<PR>& a) {
+  UChk::require_lt<2>(a);
+  uint32_t al[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) al[i] = (uint32_t)a.l[i];
+  return u_words_lt2p_to_std<PR>(al);
+}
 
 // N-form value < 32p  ->  canonical [0, p) in the 8 x 32 memory format, without a multiplication by one:
 // q = floor(v / p) is estimated from the top limb (v >> 232 against p >> 232, an underestimate by at most 2),
@@ -143,18 +182,23 @@ template <class PR>
 ZK_HD Fp<PR> u_to_std_lt32p(const FpU<PR>& a) {
   constexpr uint32_t p_top = UParams<PR>::P(8);                         // p >> 232 (22 bits)
   constexpr uint32_t magic = (uint32_t)(0x100000000ull / (p_top + 1));  // floor(2^32 / (p_top + 1))
-  const uint32_t q = (uint32_t)(((uint64_t)a.l[8] * magic) >> 32);      // <= floor(v / p), >= floor(v / p) - 2; a.l[8] < 2^28
-  FpU<PR> r;
+  UChk::require_lt<32>(a);
+  // (from here on plain words: signed carries and a borrow test that wraps on purpose)
+  uint32_t al[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) al[i] = (uint32_t)a.l[i];
+  const uint32_t q = (uint32_t)(((uint64_t)al[8] * magic) >> 32);       // <= floor(v / p), >= floor(v / p) - 2; a.l[8] < 2^28
+  uint32_t rl[9];
   int64_t carry = 0;
   for_limbs<9>([&](auto ic) {
     constexpr int i = decltype(ic)::value;
     constexpr uint32_t pi = UParams<PR>::P(i);
-    const int64_t t = (int64_t)a.l[i] - (int64_t)((uint64_t)q * pi) + carry;
+    const int64_t t = (int64_t)al[i] - (int64_t)((uint64_t)q * pi) + carry;
     if constexpr (i < 8) {
-      r.l[i] = (uint32_t)t & U_MASK;
+      rl[i] = (uint32_t)t & U_MASK;
       carry = t >> U_BITS;  // arithmetic shift: floor division
     } else {
-      r.l[i] = (uint32_t)t;  // the total is non-negative and < 3p
+      rl[i] = (uint32_t)t;  // the total is non-negative and < 3p
     }
   });
   // r < 3p: one conditional subtraction brings it below 2p, u_to_std_lt2p does the last one
@@ -163,13 +207,13 @@ ZK_HD Fp<PR> u_to_std_lt32p(const FpU<PR>& a) {
   for_limbs<9>([&](auto ic) {
     constexpr int i = decltype(ic)::value;
     constexpr uint32_t pi = UParams<PR>::P(i);
-    const uint32_t t = r.l[i] - pi - borrow;
+    const uint32_t t = rl[i] - pi - borrow;
     borrow = t >> 31;
     d[i] = (i < 8) ? (t & U_MASK) : t;
   });
 #pragma unroll
-  for (int i = 0; i < 9; ++i) r.l[i] = borrow ? r.l[i] : d[i];
-  return u_to_std_lt2p(r);
+  for (int i = 0; i < 9; ++i) rl[i] = borrow ? rl[i] : d[i];
+  return u_words_lt2p_to_std<PR>(rl);
 }
 
 // limbwise sum; limb bounds add, value bounds add.  No normalisation.
@@ -178,6 +222,7 @@ ZK_HD FpU<PR> u_add(const FpU<PR>& a, const FpU<PR>& b) {
   FpU<PR> r;
 #pragma unroll
   for (int i = 0; i < 9; ++i) r.l[i] = a.l[i] + b.l[i];
+  UChk::sum(r, a, b);
   return r;
 }
 
@@ -186,6 +231,7 @@ ZK_HD FpU<PR> u_dbl(const FpU<PR>& a) {
   FpU<PR> r;
 #pragma unroll
   for (int i = 0; i < 9; ++i) r.l[i] = a.l[i] << 1;
+  UChk::sum(r, a, a);
   return r;
 }
 
@@ -210,18 +256,65 @@ struct USubConst {
   }
 };
 
-// r = a + k*p - b, carried to N-form.
+// r = a + k*p - b, NOT carried: for a consumer that takes limbs above 2^29 (a product whose column sums have the room, the
+// subtrahend of another u_sub with a larger S).
 //   preconditions: limbs 0..7 of b < S * 2^29;  value(b) <= K * p;  limbs 0..7 of a < 2^32 - (S+1) * 2^29 - 2^4.
-//   result: N-form, value = value(a) + K*p - value(b)  (< value(a) + K*p).
+//   result: value = value(a) + K*p - value(b)  (< value(a) + K*p);  limbs 0..7 in [0, max_limb(a) + (S+1) * 2^29).
+//   Limb 8 is a.l[8] + (K p >> 232) - S - b.l[8] in u32 arithmetic: it is the true (non-negative) top limb only if
+//   b.l[8] <= a.l[8] + (K p >> 232) - S, which a caller that multiplies by the result owes (value(b) well below K p; the bound
+//   checker tests exactly this difference).  u_sub below carries, after which the top limb is exact whenever the value is >= 0.
 template <int K, int S, class PR>
-ZK_HD FpU<PR> u_sub(const FpU<PR>& a, const FpU<PR>& b) {
+ZK_HD FpU<PR> u_sub_lazy(const FpU<PR>& a, const FpU<PR>& b) {
+  UChk::sub_pre<K, S>(a, b);
   FpU<PR> t;
   for_limbs<9>([&](auto ic) {
     constexpr int i = decltype(ic)::value;
     constexpr uint32_t kc = USubConst<PR, K, S>::limb(i);
     t.l[i] = a.l[i] + kc - b.l[i];
   });
-  return u_carry(t);
+  UChk::sub_lazy<K>(t, a);
+  return t;
+}
+
+// r = a + k*p - b, carried to N-form.
+//   preconditions: those of u_sub_lazy.
+//   result: N-form, value = value(a) + K*p - value(b)  (< value(a) + K*p).
+template <int K, int S, class PR>
+ZK_HD FpU<PR> u_sub(const FpU<PR>& a, const FpU<PR>& b) {
+  FpU<PR> r = u_carry(u_sub_lazy<K, S>(a, b));
+  UChk::carried_nonneg(r);
+  return r;
+}
+
+// x or -x in u32 arithmetic, the signed limb of a sum that is carried afterwards:  -x = (x ^ m) - m  with the mask m = neg ? ~0 : 0.
+// On the device the mask is pinned in a VGPR by an empty asm statement (as u_mad pins its sums): seen through, hipcc turns every limb
+// back into a subtraction and a select, one instruction more per limb.
+ZK_HD uint32_t u_sign_mask(bool neg) {
+  uint32_t m = 0u - (uint32_t)neg;
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("" : "+v"(m));
+#endif
+  return m;
+}
+// r = K*p + (neg ? -a : a) - b, carried to N-form: the sign of a is applied limb by limb inside the sum, where the mixed addition forms
+// R = (+/-) S2 - Y1, instead of to a whole coordinate (a subtraction from p with its carry chain, then nine selects) before the product.
+//   preconditions: limbs 0..7 of a and of b < 2^29 (N-form), so that K p in the S = 2 form keeps every limb sum non-negative;
+//                  value(a) + value(b) <= K * p.
+//   result: N-form, value = K*p +/- value(a) - value(b)  in [0, K*p + value(a)).
+template <int K, class PR>
+ZK_HD FpU<PR> u_sub_signed(const FpU<PR>& a, bool neg, const FpU<PR>& b) {
+  UChk::sub_signed_pre<K>(a, b);
+  FpU<PR> t;
+  const uint32_t m = u_sign_mask(neg);
+  for_limbs<9>([&](auto ic) {
+    constexpr int i = decltype(ic)::value;
+    constexpr uint32_t kc = USubConst<PR, K, 2>::limb(i);
+    t.l[i] = ((a.l[i] ^ m) - m) + kc - b.l[i];
+  });
+  UChk::sub_lazy<K>(t, a);
+  FpU<PR> r = u_carry(t);
+  UChk::carried_nonneg(r);
+  return r;
 }
 
 // acc += a * b.  With ZK_CHAIN_MAD (defined by a translation unit before it includes this header) every accumulation
@@ -232,8 +325,8 @@ ZK_HD FpU<PR> u_sub(const FpU<PR>& a, const FpU<PR>& b) {
 // 4 waves per SIMD the chain latency is hidden (msm_accumulate_kernel<Fq> 61.3 -> 59.0 ms, ntt_pass_kernel -2 %), the
 // register-heavier kernels (Fq2 accumulation, the windowed scalar multiplications) lose.  The s_nop hipcc pads after
 // each asm statement issues on the scalar port and costs next to nothing.
-ZK_HD void u_mad(uint64_t& acc, uint32_t a, uint32_t b) {
-  acc += (uint64_t)a * b;
+ZK_HD void u_mad(uacc_t& acc, ulimb_t a, ulimb_t b) {
+  acc += (uacc_t)a * b;
 #if defined(__HIP_DEVICE_COMPILE__) && defined(ZK_CHAIN_MAD)
   asm("" : "+v"(acc));
 #endif
@@ -247,9 +340,10 @@ ZK_HD void u_mad(uint64_t& acc, uint32_t a, uint32_t b) {
 // free to schedule the 162 of them.
 template <class PR>
 ZK_HD FpU<PR> u_mul(const FpU<PR>& a, const FpU<PR>& b) {
-  uint32_t m[9];
+  UChk::mul_pre(a, b);
+  ulimb_t m[9];
   FpU<PR> r;
-  uint64_t acc = 0;
+  uacc_t acc = 0;
   for_limbs<17>([&](auto kc) {
     constexpr int k = decltype(kc)::value;
     for_limbs<9>([&](auto ic) {
@@ -267,14 +361,15 @@ ZK_HD FpU<PR> u_mul(const FpU<PR>& a, const FpU<PR>& b) {
     });
     if constexpr (k < 9) {
       constexpr uint32_t p0 = UParams<PR>::P(0);
-      m[k] = ((uint32_t)acc * UParams<PR>::INV) & U_MASK;
+      m[k] = ((ulimb_t)acc * UParams<PR>::INV) & U_MASK;
       u_mad(acc, m[k], p0);  // low 29 bits are now zero
     } else {
-      r.l[k - 9] = (uint32_t)acc & U_MASK;
+      r.l[k - 9] = (ulimb_t)acc & U_MASK;
     }
     acc >>= U_BITS;
   });
-  r.l[8] = (uint32_t)acc;
+  r.l[8] = (ulimb_t)acc;
+  UChk::mul(r, a, b);
   return r;
 }
 
@@ -282,9 +377,9 @@ ZK_HD FpU<PR> u_mul(const FpU<PR>& a, const FpU<PR>& b) {
 // `acc` for column k through the callback and this adds the m_i * p_j terms and extracts the limb.
 template <class PR, class ProductTerms>
 ZK_HD FpU<PR> u_montgomery_columns(ProductTerms&& terms) {
-  uint32_t m[9];
+  ulimb_t m[9];
   FpU<PR> r;
-  uint64_t acc = 0;
+  uacc_t acc = 0;
   for_limbs<17>([&](auto kc) {
     constexpr int k = decltype(kc)::value;
     terms(kc, acc);
@@ -298,14 +393,14 @@ ZK_HD FpU<PR> u_montgomery_columns(ProductTerms&& terms) {
     });
     if constexpr (k < 9) {
       constexpr uint32_t p0 = UParams<PR>::P(0);
-      m[k] = ((uint32_t)acc * UParams<PR>::INV) & U_MASK;
+      m[k] = ((ulimb_t)acc * UParams<PR>::INV) & U_MASK;
       u_mad(acc, m[k], p0);  // low 29 bits are now zero
     } else {
-      r.l[k - 9] = (uint32_t)acc & U_MASK;
+      r.l[k - 9] = (ulimb_t)acc & U_MASK;
     }
     acc >>= U_BITS;
   });
-  r.l[8] = (uint32_t)acc;
+  r.l[8] = (ulimb_t)acc;
   return r;
 }
 
@@ -314,10 +409,11 @@ ZK_HD FpU<PR> u_montgomery_columns(ProductTerms&& terms) {
 // the Montgomery terms per column stay far below 2^64).   result as u_mul.
 template <class PR>
 ZK_HD FpU<PR> u_sqr(const FpU<PR>& a) {
-  uint32_t a2[9];
+  UChk::sqr_pre(a);
+  ulimb_t a2[9];
 #pragma unroll
   for (int i = 0; i < 9; ++i) a2[i] = a.l[i] << 1;
-  return u_montgomery_columns<PR>([&](auto kc, uint64_t& acc) {
+  FpU<PR> r = u_montgomery_columns<PR>([&](auto kc, uacc_t& acc) {
     constexpr int k = decltype(kc)::value;
     for_limbs<9>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
@@ -328,14 +424,19 @@ ZK_HD FpU<PR> u_sqr(const FpU<PR>& a) {
       }
     });
   });
+  UChk::mul(r, a, a);
+  return r;
 }
 
 // (a*b + c*d) * 2^-261 mod p with ONE Montgomery reduction: 162 + 81 mads instead of 324.
-//   preconditions: all four operands N-form (18 products < 2^58 per column);
+//   preconditions: max_limb(a) max_limb(b) + max_limb(c) max_limb(d) <= 6 * 2^58 (all four N-form: 2 * 2^58; one operand with limbs
+//                  < 2^30, the others N-form: 3 * 2^58), so that a column (9 of each product, 9 Montgomery terms < 2^58, the carry
+//                  < 2^36) stays below 63 * 2^58 + 2^36 < 2^64;
 //   result: N-form, value < (value(a) value(b) + value(c) value(d)) / 2^261 + p.
 template <class PR>
 ZK_HD FpU<PR> u_mul2(const FpU<PR>& a, const FpU<PR>& b, const FpU<PR>& c, const FpU<PR>& d) {
-  return u_montgomery_columns<PR>([&](auto kc, uint64_t& acc) {
+  UChk::mul2_pre(a, b, c, d);
+  FpU<PR> r = u_montgomery_columns<PR>([&](auto kc, uacc_t& acc) {
     constexpr int k = decltype(kc)::value;
     for_limbs<9>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
@@ -346,6 +447,8 @@ ZK_HD FpU<PR> u_mul2(const FpU<PR>& a, const FpU<PR>& b, const FpU<PR>& c, const
       }
     });
   });
+  UChk::mul(r, a, b, c, d);
+  return r;
 }
 
 // (a*b + c*d + e*f) * 2^-261 mod p with ONE Montgomery reduction.
@@ -353,7 +456,7 @@ ZK_HD FpU<PR> u_mul2(const FpU<PR>& a, const FpU<PR>& b, const FpU<PR>& c, const
 //   result: N-form, value < (sum of the three value products) / 2^261 + p.
 template <class PR>
 ZK_HD FpU<PR> u_mul3(const FpU<PR>& a, const FpU<PR>& b, const FpU<PR>& c, const FpU<PR>& d, const FpU<PR>& e, const FpU<PR>& f) {
-  return u_montgomery_columns<PR>([&](auto kc, uint64_t& acc) {
+  return u_montgomery_columns<PR>([&](auto kc, uacc_t& acc) {
     constexpr int k = decltype(kc)::value;
     for_limbs<9>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
@@ -373,7 +476,7 @@ ZK_HD FpU<PR> u_mul3(const FpU<PR>& a, const FpU<PR>& b, const FpU<PR>& c, const
 template <class PR>
 ZK_HD FpU<PR> u_mul4(const FpU<PR>& a, const FpU<PR>& b, const FpU<PR>& c, const FpU<PR>& d, const FpU<PR>& e, const FpU<PR>& f,
                      const FpU<PR>& g, const FpU<PR>& h) {
-  return u_montgomery_columns<PR>([&](auto kc, uint64_t& acc) {
+  return u_montgomery_columns<PR>([&](auto kc, uacc_t& acc) {
     constexpr int k = decltype(kc)::value;
     for_limbs<9>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
@@ -408,8 +511,8 @@ struct UShoup {
 //   (the columns 0 .. 6 of a * wq are dropped: their sum is < 7 * 2^60 * 2^174 * 1.01 < 2^238, i.e. below 2^-23 of 2^261)
 template <class PR>
 ZK_HD FpU<PR> u_mul_shoup(const FpU<PR>& a, const FpU<PR>& w, const FpU<PR>& wq) {
-  uint32_t q[9];
-  uint64_t acc = 0;
+  ulimb_t q[9];
+  uacc_t acc = 0;
   for_limbs<10>([&](auto kc) {
     constexpr int k = 7 + decltype(kc)::value;                              // columns 7 .. 16 of a * wq
     for_limbs<9>([&](auto ic) {
@@ -417,10 +520,10 @@ ZK_HD FpU<PR> u_mul_shoup(const FpU<PR>& a, const FpU<PR>& w, const FpU<PR>& wq)
       constexpr int j = k - i;
       if constexpr (j >= 0 && j < 9) u_mad(acc, a.l[i], wq.l[j]);
     });
-    if constexpr (k >= 9) q[k - 9] = (uint32_t)acc & U_MASK;
+    if constexpr (k >= 9) q[k - 9] = (ulimb_t)acc & U_MASK;
     acc >>= U_BITS;
   });
-  q[8] = (uint32_t)acc;                                                     // column 17: the carry (a * wq < 2^261 * 2^261)
+  q[8] = (ulimb_t)acc;                                                      // column 17: the carry (a * wq < 2^261 * 2^261)
   FpU<PR> r;
   acc = 0;
   for_limbs<9>([&](auto kc) {
@@ -438,7 +541,7 @@ ZK_HD FpU<PR> u_mul_shoup(const FpU<PR>& a, const FpU<PR>& w, const FpU<PR>& wq)
         u_mad(acc, q[i], pb);
       }
     });
-    r.l[k] = (uint32_t)acc & U_MASK;                                        // (k == 8: mod 2^261; the value is < 2p < 2^255)
+    r.l[k] = (ulimb_t)acc & U_MASK;                                         // (k == 8: mod 2^261; the value is < 2p < 2^255)
     acc >>= U_BITS;
   });
   return r;
@@ -486,7 +589,7 @@ ZK_HD FpU<PR> u_shoup_quotient(const uint32_t w_plain[8]) {
 // value == 0 mod p for an N-form value < 2p  (i.e. value in {0, p})
 template <class PR>
 ZK_HD bool u_is_zero_lt2p(const FpU<PR>& a) {
-  uint32_t z = 0, e = 0;
+  ulimb_t z = 0, e = 0;
   for_limbs<9>([&](auto ic) {
     constexpr int i = decltype(ic)::value;
     constexpr uint32_t pi = UParams<PR>::P(i);
@@ -539,6 +642,7 @@ struct UPow2 {
       constexpr uint32_t v = limb(i);
       r.l[i] = v;
     });
+    UChk::canonical(r);
     return r;
   }
 };

@@ -31,6 +31,24 @@ int msm_g1_dense_device(const void* d_bases, const void* d_bases2, const void* d
   return rc;
 }
 
+// the dense call with the bucket tap of msm_host.hpp set: what the accumulate stage left, for mi355zk_selftest_g1_msm_buckets_dev
+int msm_g1_buckets_device(const void* d_bases, const void* d_scalars, uint64_t n, hipStream_t st, uint64_t out_xyz[12], uint32_t* n_buckets, uint32_t* n_vals,
+                          uint32_t* first, uint32_t* last, size_t cap_buckets, uint32_t* vals, size_t cap_vals, uint64_t* records) {
+  MsmBucketTap tap;
+  g_msm_bucket_tap = &tap;
+  const int rc = msm_g1_dense_device(d_bases, nullptr, d_scalars, n, st, out_xyz, nullptr);
+  g_msm_bucket_tap = nullptr;
+  if (rc != ZK_OK) return rc;
+  *n_buckets = tap.n_buckets;
+  *n_vals = (uint32_t)tap.vals.size();
+  if (tap.n_buckets > cap_buckets || tap.vals.size() > cap_vals) return ZK_ERR_BAD_ARGS;   // (the two counts tell the caller what to bring)
+  std::memcpy(first, tap.first.data(), tap.first.size() * 4);
+  std::memcpy(last, tap.last.data(), tap.last.size() * 4);
+  if (!tap.vals.empty()) std::memcpy(vals, tap.vals.data(), tap.vals.size() * 4);
+  std::memcpy(records, tap.records.data(), tap.records.size() * 8);
+  return ZK_OK;
+}
+
 int segsum_g1_device(const void* d_points, uint64_t nnz, const uint32_t* d_row_ptr, uint32_t n_rows, hipStream_t st, void* d_out) {
   return segsum_device<Fq>((const G1Affine*)d_points, nnz, d_row_ptr, n_rows, st, (G1Affine*)d_out);
 }

@@ -320,6 +320,33 @@ int msm_finish_set(const MsmCall<F>& A, SmallWsLease& lease, std::unique_lock<st
   return (int)ZK_OK;
 }
 
+// Self-test tap (mi355zk_selftest_g1_msm_buckets_dev): a caller that sets this pointer for its thread gets, from a single-chunk call, the partition's
+// index lists (first / last per bucket, the signed base indices) and the bucket records as the accumulation left them, copied to the host after the
+// accumulate stage and before the reduction.  Nothing else reads it; the product's callers leave it null.
+struct MsmBucketTap {
+  uint32_t n_buckets = 0;
+  std::vector<uint32_t> first, last, vals;
+  std::vector<uint64_t> records;   // n_buckets records, sizeof(XYZZ<F>) / 8 words each
+};
+inline thread_local MsmBucketTap* g_msm_bucket_tap = nullptr;
+template <class F>
+int msm_tap_buckets(const MsmCall<F>& A, MsmBucketTap& T) {
+  const uint32_t nb = A.plan.n_buckets;
+  T.n_buckets = nb;
+  T.first.resize(nb), T.last.resize(nb), T.records.resize((size_t)nb * sizeof(XYZZ<F>) / 8);
+  ZK_HIP(hipMemcpyAsync(T.first.data(), A.ws.first, (size_t)nb * 4, hipMemcpyDeviceToHost, A.st));
+  ZK_HIP(hipMemcpyAsync(T.last.data(), A.ws.last, (size_t)nb * 4, hipMemcpyDeviceToHost, A.st));
+  ZK_HIP(hipMemcpyAsync(T.records.data(), A.ws.buckets, (size_t)nb * sizeof(XYZZ<F>), hipMemcpyDeviceToHost, A.st));
+  ZK_HIP(hipStreamSynchronize(A.st));
+  uint32_t top = 0;
+  for (uint32_t b = 0; b < nb; ++b)
+    if (T.last[b] > T.first[b] && T.last[b] > top) top = T.last[b];
+  T.vals.resize(top);
+  if (top) ZK_HIP(hipMemcpyAsync(T.vals.data(), A.ws.vals_b, (size_t)top * 4, hipMemcpyDeviceToHost, A.st));
+  ZK_HIP(hipStreamSynchronize(A.st));
+  return ZK_OK;
+}
+
 template <class F>
 int msm_device(const Affine<F>* d_bases, uint64_t n_bases, uint64_t base_offset, const uint32_t* d_scalars, uint64_t n,
                const uint32_t* d_density, const uint32_t* d_dprefix, hipStream_t st, Jacobian<F>* out, long long* err_index_out,
@@ -400,6 +427,10 @@ int msm_device(const Affine<F>* d_bases, uint64_t n_bases, uint64_t base_offset,
     if (rc == ZK_OK) rc = launch_partition(A, A.ws, C);
     if (rc == ZK_OK) rc = launch_accumulate(A, C, d_bases, c > 0);
     if (rc) return rc;
+  }
+  if (g_msm_bucket_tap) {
+    if (P.chunks.size() != 1) return ZK_ERR_BAD_ARGS;
+    if (int trc = msm_tap_buckets(A, *g_msm_bucket_tap)) return trc;
   }
   // bucket reduction, the copy back and the host join: once per base vector
   const bool two_sets = d_bases2 != nullptr && out2 != nullptr;

@@ -69,6 +69,7 @@ SIGNATURES = {
     "mi355zk_bn254_g1_merge_pairs_random": (_i, [_vp, _vp, _sz, _u32p, C.c_uint64, _vp, _vp]),
     "mi355zk_bn254_g2_merge_pairs_random": (_i, [_vp, _vp, _sz, _u32p, C.c_uint64, _vp, _vp]),
     "mi355zk_bn254_g1_dense_multiexp_dev": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "mi355zk_selftest_g1_msm_buckets_dev": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "mi355zk_bn254_g2_dense_multiexp_dev": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "mi355zk_bn254_g1_merge_pairs_dev": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "mi355zk_bn254_g2_merge_pairs_dev": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
