@@ -272,7 +272,10 @@ int mi355zk_msm_window_bits(size_t n_scalars, int *n_windows);
 int mi355zk_msm_window_bits_groups(size_t n_scalars, uint32_t window_groups, int *n_windows);
 
 /* ---- Fr NTT.  Replaces bellman/src/domain.rs:263 `best_fft` for T = Scalar<Bn256>:
- * a[0..2^log_n) in place, natural order in and out, `omega` of order 2^log_n (Montgomery form). */
+ * a[0..2^log_n) in place, natural order in and out, `omega` of order 2^log_n (Montgomery form).
+ * Operand range, for every transform and domain entry point below: the elements of `a` (and omega and the scale factors) are CANONICAL
+ * Montgomery Fr, stored words < r, unchecked.  That is the load state the kernels' lazy-reduction bounds are derived from
+ * (csrc/ntt_butterfly.hpp; tests/cpp/test_ntt_bounds_host.cpp); the outputs are canonical again. */
 int mi355zk_bn254_fr_ntt(uint64_t *a, uint32_t log_n, const uint64_t omega[4]);
 /* EvaluationDomain::{fft, ifft, coset_fft, icoset_fft} (domain.rs:154-203) with the constants
  * `from_coeffs` derives for m = 2^log_n (domain.rs:84-98: omega, omegainv, geninv = 7^-1, minv). */

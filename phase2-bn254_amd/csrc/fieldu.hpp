@@ -40,7 +40,7 @@ ZK_HD void for_limbs(F&& f) {
 
 // ---- limb and accumulator types, and the bound hooks ----
 // The product computes on ulimb_t = uint32_t limbs and uacc_t = uint64_t column sums, and every UChk hook below is an empty function.
-// The host bound checker (tests/cpp/u_interval.hpp, tests/cpp/test_u_bounds_host.cpp) defines ZK_U_BOUNDS_CHECK and supplies the three
+// The host bound checker (tests/cpp/u_interval.hpp, tests/cpp/test_u_bounds_host.cpp, tests/cpp/test_ntt_bounds_host.cpp) defines ZK_U_BOUNDS_CHECK and supplies the three
 // names itself: limbs and sums that carry their value together with a worst-case integer interval, a value bound "< k p" per element
 // (UValueBound, the base of FpU), and hooks that TEST the preconditions stated at the functions below with what the callers pass and
 // NOTE the stated results.  The lines that run are these: the checker instantiates the templates of this file and of curveu.hpp.
@@ -64,6 +64,19 @@ struct UChk {
   template <int K, class... T> ZK_HD static void sub_lazy(T&&...) {}          // value(r) <= value(a) + K p, limbs as computed
   template <class... T> ZK_HD static void carried_nonneg(T&&...) {}           // r N-form with value(r) >= 0: the top limb is exact again
   template <int K, class... T> ZK_HD static void require_lt(T&&...) {}        // N-form and value < K p (the u_to_std_* preconditions)
+};
+#endif
+// The hooks of u_mul_shoup, u_mul3 / u_mul4 and u_from_std.  A checker states that it implements them by defining ZK_U_BOUNDS_CHECK as 2 (its
+// UChk then has these five members); for the product, and for a checker that defines it as 1, they are empty.
+#if defined(ZK_U_BOUNDS_CHECK) && ZK_U_BOUNDS_CHECK >= 2
+using UChk2 = UChk;
+#else
+struct UChk2 {
+  template <class... T> ZK_HD static void muln_pre(T&&...) {}       // u_mul3 / u_mul4's precondition: every operand N-form
+  template <class... T> ZK_HD static void muln(T&&...) {}           // r = the Montgomery result of a b + c d + e f (+ g h): value and top limb
+  template <class... T> ZK_HD static void shoup_pre(T&&...) {}      // u_mul_shoup's preconditions on (a, w, wq)
+  template <class... T> ZK_HD static void shoup(T&&...) {}          // r = the Shoup product: N-form, value < 2p
+  template <class... T> ZK_HD static void from_std(T&&...) {}       // r re-packed from the memory format: canonical by that format's contract
 };
 #endif
 
@@ -116,6 +129,7 @@ ZK_HD FpU<PR> u_from_std(const Fp<PR>& a) {
     uint64_t two = (uint64_t)a.l[word] | (word + 1 < 8 ? (uint64_t)a.l[word + 1] << 32 : 0ull);
     r.l[i] = (uint32_t)(two >> off) & U_MASK;
   }
+  UChk2::from_std(r);
   return r;
 }
 
@@ -456,7 +470,8 @@ ZK_HD FpU<PR> u_mul2(const FpU<PR>& a, const FpU<PR>& b, const FpU<PR>& c, const
 //   result: N-form, value < (sum of the three value products) / 2^261 + p.
 template <class PR>
 ZK_HD FpU<PR> u_mul3(const FpU<PR>& a, const FpU<PR>& b, const FpU<PR>& c, const FpU<PR>& d, const FpU<PR>& e, const FpU<PR>& f) {
-  return u_montgomery_columns<PR>([&](auto kc, uacc_t& acc) {
+  UChk2::muln_pre(a, b, c, d, e, f);
+  FpU<PR> r = u_montgomery_columns<PR>([&](auto kc, uacc_t& acc) {
     constexpr int k = decltype(kc)::value;
     for_limbs<9>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
@@ -468,6 +483,8 @@ ZK_HD FpU<PR> u_mul3(const FpU<PR>& a, const FpU<PR>& b, const FpU<PR>& c, const
       }
     });
   });
+  UChk2::muln(r, a, b, c, d, e, f);
+  return r;
 }
 
 // (a*b + c*d + e*f + g*h) * 2^-261 mod p with ONE Montgomery reduction (Fq2 products of sums).
@@ -476,7 +493,8 @@ ZK_HD FpU<PR> u_mul3(const FpU<PR>& a, const FpU<PR>& b, const FpU<PR>& c, const
 template <class PR>
 ZK_HD FpU<PR> u_mul4(const FpU<PR>& a, const FpU<PR>& b, const FpU<PR>& c, const FpU<PR>& d, const FpU<PR>& e, const FpU<PR>& f,
                      const FpU<PR>& g, const FpU<PR>& h) {
-  return u_montgomery_columns<PR>([&](auto kc, uacc_t& acc) {
+  UChk2::muln_pre(a, b, c, d, e, f, g, h);
+  FpU<PR> r = u_montgomery_columns<PR>([&](auto kc, uacc_t& acc) {
     constexpr int k = decltype(kc)::value;
     for_limbs<9>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
@@ -489,6 +507,8 @@ ZK_HD FpU<PR> u_mul4(const FpU<PR>& a, const FpU<PR>& b, const FpU<PR>& c, const
       }
     });
   });
+  UChk2::muln(r, a, b, c, d, e, f, g, h);
+  return r;
 }
 
 // ---- product by a CONSTANT with a precomputed quotient (Shoup / Barrett with the quotient of the constant) ----
@@ -511,6 +531,7 @@ struct UShoup {
 //   (the columns 0 .. 6 of a * wq are dropped: their sum is < 7 * 2^60 * 2^174 * 1.01 < 2^238, i.e. below 2^-23 of 2^261)
 template <class PR>
 ZK_HD FpU<PR> u_mul_shoup(const FpU<PR>& a, const FpU<PR>& w, const FpU<PR>& wq) {
+  UChk2::shoup_pre(a, w, wq);
   ulimb_t q[9];
   uacc_t acc = 0;
   for_limbs<10>([&](auto kc) {
@@ -544,6 +565,7 @@ ZK_HD FpU<PR> u_mul_shoup(const FpU<PR>& a, const FpU<PR>& w, const FpU<PR>& wq)
     r.l[k] = (ulimb_t)acc & U_MASK;                                         // (k == 8: mod 2^261; the value is < 2p < 2^255)
     acc >>= U_BITS;
   });
+  UChk2::shoup(r, a);
   return r;
 }
 

@@ -18,11 +18,12 @@
 //
 // U-form bookkeeping (fieldu.hpp): data stays in the memory format's 2^256 domain the whole time -- every
 // product is by a table twiddle, kept as the PLAIN integer w with its quotient floor(w 2^261 / p), and
-// u_mul_shoup(data, w, wq) returns data*w itself, below 2p (round 4; rounds 1-3: Montgomery products by
+// the Shoup product of fieldu.hpp returns data*w itself, below 2p (round 4; rounds 1-3: Montgomery products by
 // twiddles in the 2^261 domain, 180 multiplier instructions against 143) -- so loads and stores only
-// re-pack bits.  DIT butterflies (a + w b, a - w b) grow values linearly: V_s <= V_0 + 2 s p <= 24p after
-// 10 stages (30p with the skipped twiddle-one products), far below the 160p the product admits; limbs
-// are carried every 4th stage (the bound of each call is noted at the call).
+// re-pack bits.  DIT butterflies (a + w b, a - w b) grow values linearly: V_s <= V_0 + 2 s p <= 22p after
+// 10 stages without a skipped product, 30p with the skipped twiddle-one products (values double there), far below
+// the 160p the product admits and below the 32p of the closing reduction; limbs are carried every 4th stage.  The
+// arithmetic and its bounds are stated once, in ntt_butterfly.hpp, and derived by tests/cpp/test_ntt_bounds_host.cpp.
 // The mathematical result X[k] = sum_i a[i] w^(ik) is unique and the stored elements are fully
 // reduced, so the output bytes are identical to serial_fft's.
 #define ZK_CHAIN_MAD 1  // fieldu.hpp u_mad: one dependent mad chain per column (measured faster in this TU)
@@ -36,6 +37,7 @@
 #include <vector>
 
 #include "fieldu.hpp"
+#include "ntt_butterfly.hpp"  // TwU, tw_mul, tw_make; NttSchedule, ntt_bf and every other line of field arithmetic a pass runs
 #include "device_util.hpp"
 #include "ntt_plan.hpp"  // NttPassParams, NttBatch, the NTT_* constants; NttKnobs and the planner
 
@@ -49,10 +51,6 @@ namespace {
 struct alignas(8) UTab {
   uint32_t l[18];
 };
-struct TwU {
-  FrU w, q;
-};
-
 __device__ __forceinline__ TwU tab_load(const UTab* p) {
   const uint2* s = reinterpret_cast<const uint2*>(p);   // (hipcc merges neighbours into 16-byte loads where the address allows)
   uint32_t v[18];
@@ -66,16 +64,6 @@ __device__ __forceinline__ TwU tab_load(const UTab* p) {
 #pragma unroll
   for (int i = 0; i < 9; ++i) { r.w.l[i] = v[i]; r.q.l[i] = v[9 + i]; }
   return r;
-}
-// x * (the table constant): the value itself (no Montgomery factor), < 2p for x < 160p with limbs < 2^31
-__device__ __forceinline__ FrU tw_mul(const FrU& x, const TwU& t) { return u_mul_shoup(x, t.w, t.q); }
-
-// entry for the plain canonical integer c (8 x 32-bit words)
-ZK_HD TwU tw_make(const Fr& c_plain) {
-  TwU t;
-  t.w = u_from_std(c_plain);
-  t.q = u_shoup_quotient<FrParams>(c_plain.l);
-  return t;
 }
 __device__ __forceinline__ void tab_store(UTab* p, const TwU& t) {
   UTab e;
@@ -152,9 +140,8 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_kernel(const Fr* __restr
                                                               const UTab* __restrict__ postB, TwU post_c, const UTab* __restrict__ twF, NttBatch BP) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   constexpr uint32_t np = 1u << LOG_NP;
-  // twiddle-one products are skipped in stages 0 .. SKIP_MAX: rows longer than 2^10 give up stage 2 (a skipped stage doubles the
-  // value bound instead of adding 2p: 16p + 2 (LOG_NP - 3) p would pass the 32p the closing reduction allows; 10p + 2 (LOG_NP - 3) p does not)
-  constexpr uint32_t SKIP_MAX = LOG_NP > 10 ? 1 : 2;
+  // twiddle-one products are skipped in the stages the schedule allows (ntt_butterfly.hpp: rows longer than 2^10 give up stage 2)
+  using SCH = NttSchedule<LOG_NP>;
   constexpr uint32_t pitch = np;
   const uint32_t plane = P.g * pitch;
   const uint32_t elems = P.g * np;
@@ -180,40 +167,24 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_kernel(const Fr* __restr
     if (P.load_x_fastest) { x = e & (np - 1); g = e >> LOG_NP; }
     else { g = e % P.g; x = e / P.g; }
     const uint64_t gi = in_base + x * P.in_xs + g * P.in_gs;
-    FrU v = u_from_std(gload(in + gi));                                   // < p, N
+    FrU v = ntt_load(gload(in + gi));                                     // < p, N
     if (P.pre == 1) {                                                     // distribute_powers (domain.rs:176-189)
-      v = tw_mul(v, tab_load(preA + (gi >> P.pre_h)));                    // g^i = A[i >> h] * B[i & mask]: two products by constants
-      v = tw_mul(v, tab_load(preB + (gi & ((1ull << P.pre_h) - 1))));     // < 2p, N
+      v = ntt_pre1(v, tab_load(preA + (gi >> P.pre_h)), [&] { return tab_load(preB + (gi & ((1ull << P.pre_h) - 1))); });   // g^i = A[i >> h] * B[i & mask]: < 2p, N
     } else if (P.pre == 2) {
-      v = tw_mul(v, tab_load(preA + x));                                  // (g^S)^x: the column's g^col sits in the folded inter-pass table
+      v = ntt_pre2(v, tab_load(preA + x));                                // (g^S)^x: the column's g^col sits in the folded inter-pass table
     }
     lds_store(lds, plane, g * pitch + (swz(bitrev(x, LOG_NP)) ^ row_term(g, P.g, np)), v);
   }
   __syncthreads();
 
   // DIT stages.  Entering stage s every element has limbs < ((s & 3) + 1) * 2^29 and is < (4 + 2s) p, or < 16p + 2(s - 3)p when
-  // the twiddle-one products of stages 1 and 2 are skipped (see j_slow).
+  // the twiddle-one products of stages 1 and 2 are skipped (see j_slow): the chain is stated in ntt_butterfly.hpp and derived, stage by
+  // stage, by the host bound checker (tests/cpp/test_ntt_bounds_host.cpp).
   if constexpr (R4) {
   // (LOG_NP is a template parameter and the stage loops are static: the stage number, the skip / carry decisions and the shift amounts
   // of the index arithmetic are compile-time constants in every stage)
-  // One butterfly of stage ST on registers: (u, t) -> (u + w t, u - w t); skip: w = 1 (stage 0; twiddle index 0 of stages 1 and 2).
-  // Bounds with skipping: a skipped product leaves t as large as u, so values DOUBLE on that path: V_1 < 4p, V_2 < 8p, V_3 < 16p, and
-  // with + 2p for each of the stages 3..9: < 30p at the end (u_to_std_lt32p / the closing product allow < 32p); the subtraction
-  // constant follows (u_sub<4,1> / <8,1>).  Stage 3 is not skipped: it would take the bound past 32p.
-  auto bf = [&](auto stc, FrU& u, FrU& t, const TwU& w, bool skip) {
-    constexpr uint32_t ST = (uint32_t) decltype(stc)::value;
-    // (t < 24p with limbs < 4*2^29 either way: the skipped product only leaves t as large as u may be)
-    if (!skip) t = tw_mul(t, w);                                           // limbs < 4*2^29, < 30p: ok; < 2p, N
-    else t = u_carry(t);
-    FrU sum = u_add(u, t);                                                 // limbs grow by 2^29, value by 2p
-    if constexpr ((ST & 3) == 3) sum = u_carry(sum);
-    FrU dif;                                                               // t N; u limbs < 4*2^29 < 2^32 - 2^30 - 16: ok.  N out
-    if constexpr (ST == 1) dif = skip ? u_sub<4, 1>(u, t) : u_sub<2, 1>(u, t);        // skipped: t < 4p
-    else if constexpr (ST == 2) dif = skip ? u_sub<8, 1>(u, t) : u_sub<2, 1>(u, t);   // skipped: t < 8p
-    else dif = u_sub<2, 1>(u, t);                                          // t < 2p
-    u = sum;
-    t = dif;
-  };
+  // One butterfly of stage ST on registers (ntt_bf): (u, t) -> (u + w t, u - w t); skip: w = 1 (stage 0; twiddle index 0 of stages 1 and 2).
+  const auto bf = ntt_bf_fn<SCH>();
   constexpr uint32_t S0 = LOG_NP & 1;  // an odd number of stages: stage 0 alone (all twiddles one), then pairs
   if constexpr (S0 == 1) {
     const uint32_t half = elems >> 1;
@@ -252,14 +223,14 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_kernel(const Fr* __restr
       const uint32_t row = g * pitch, rx = row_term(g, P.g, np);
       const uint32_t ia = row + (swz(x0) ^ rx), ib = row + (swz(x0 + m) ^ rx), ic = row + (swz(x0 + 2 * m) ^ rx), id = row + (swz(x0 + 3 * m) ^ rx);
       FrU a = lds_load(lds, plane, ia), b = lds_load(lds, plane, ib), c = lds_load(lds, plane, ic), d = lds_load(lds, plane, id);
-      const bool one = s <= SKIP_MAX && j == 0;                            // stage s (s == 0: j == 0 always)
+      const bool one = SCH::may_skip(s) && j == 0;                            // stage s (s == 0: j == 0 always)
       {
         TwU w1{a, a};
         if (!one) w1 = tab_load(roots + ((uint64_t)j << (LOG_NP - 1 - s)));
         bf(std::integral_constant<int, (int)s>{}, a, b, w1, one);
         bf(std::integral_constant<int, (int)s>{}, c, d, w1, one);
       }
-      const bool one2 = s + 1 <= SKIP_MAX && j == 0;                       // stage s + 1, pair (a, c): index j
+      const bool one2 = SCH::may_skip(s + 1) && j == 0;                       // stage s + 1, pair (a, c): index j
       {
         TwU w2{a, a};
         if (!one2) w2 = tab_load(roots + ((uint64_t)j << (LOG_NP - 2 - s)));
@@ -285,14 +256,11 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_kernel(const Fr* __restr
   for_limbs<(int)LOG_NP>([&](auto sc) {
     constexpr uint32_t s = (uint32_t) decltype(sc)::value;
     constexpr uint32_t m = 1u << s;
-    constexpr bool carry_now = (s & 3) == 3;
     // Stages 1 and 2 (when a row has at least 64 blocks of 2m): the butterflies of a row are dealt to the lanes with the
     // twiddle index j SLOWEST (lane = j * blocks + block), so j is uniform over a wave and the waves with j == 0 -- twiddle
     // one: 1/2 and 1/4 of the butterflies of these stages -- skip the product.  Later stages: j fastest (unit-stride LDS).
-    // Bounds: a skipped product leaves t as large as u, so values DOUBLE on that path: V_1 < 4p, V_2 < 8p, V_3 < 16p, and
-    // with + 2p for each of the stages 3..9: < 30p at the end (u_to_std_lt32p / the closing product allow < 32p); the
-    // subtraction constant follows (u_sub<4,1> / <8,1>).  Stage 3 is not skipped: it would take the bound past 32p.
-    constexpr bool j_slow = s >= 1 && s <= SKIP_MAX && (np >> (s + 1)) >= 64;
+    // (Bounds: ntt_butterfly.hpp.)
+    constexpr bool j_slow = s >= 1 && SCH::may_skip(s) && (np >> (s + 1)) >= 64;
     for (uint32_t b = threadIdx.x; b < half; b += blockDim.x) {
       uint32_t g = b >> (LOG_NP - 1);
       uint32_t bf = b & ((np >> 1) - 1);
@@ -310,14 +278,10 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_kernel(const Fr* __restr
       uint32_t i1 = g * pitch + (swz(x0 + m) ^ rx);
       FrU u = lds_load(lds, plane, i0);
       FrU t = lds_load(lds, plane, i1);
-      // (t < 24p with limbs < 4*2^29 either way: the skipped product only leaves t as large as u may be)
-      if (s != 0 && !(j_slow && j == 0)) t = tw_mul(t, tab_load(roots + ((uint64_t)j << (LOG_NP - 1 - s))));  // limbs < 4*2^29, < 30p: ok; < 2p, N
-      else t = u_carry(t);                                                // w = 1 (stage 0; j == 0): no product
-      FrU sum = u_add(u, t);                                              // limbs grow by 2^29, value by 2p
-      if (carry_now) sum = u_carry(sum);
-      FrU dif;                                                            // t N; u limbs < 4*2^29 < 2^32 - 2^30 - 16: ok.  N out
-      if (j_slow && j == 0) dif = s == 1 ? u_sub<4, 1>(u, t) : u_sub<8, 1>(u, t);   // t < 4p (stage 1), < 8p (stage 2)
-      else dif = u_sub<2, 1>(u, t);                                       // t < 2p
+      const bool skip = (s == 0) || (j_slow && j == 0);                   // w = 1 (stage 0; j == 0): no product
+      FrU sum, dif;
+      const UTab* const tw = roots + ((uint64_t)j << (LOG_NP - 1 - s));
+      ntt_bf_to<s, SCH>(u, t, [&]() __attribute__((always_inline)) { return tab_load(tw); }, skip, sum, dif);
       lds_store(lds, plane, i0, sum);
       lds_store(lds, plane, i1, dif);
     }
@@ -335,22 +299,21 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_kernel(const Fr* __restr
       w = tab_load(twF + go);                                             // w^(k * col), streamed: one product instead of two
     } else if (P.tw_mul != 0) {
       uint64_t ex = P.tw_mul * k * (lo * P.g + g);
-      v = tw_mul(v, tab_load(twA + (ex >> P.tw_h)));                      // w^ex = A[ex >> h] * B[ex & mask]
+      v = ntt_post_mul(v, tab_load(twA + (ex >> P.tw_h)));                // w^ex = A[ex >> h] * B[ex & mask]
       w = tab_load(twB + (ex & ((1ull << P.tw_h) - 1)));
     } else if (P.post == 2) {                                             // minv * ginv^k (icoset_fft, domain.rs:197-203)
-      v = tw_mul(v, tab_load(postA + (go >> P.post_h)));
-      v = tw_mul(v, tab_load(postB + (go & ((1ull << P.post_h) - 1))));
+      v = ntt_post_mul2(v, tab_load(postA + (go >> P.post_h)), [&] { return tab_load(postB + (go & ((1ull << P.post_h) - 1))); });
       w = post_c;
     } else if (P.post == 3) {                                             // plain fft / coset_fft: nothing to multiply by --
-      gstore(out + go, u_to_std_lt32p(u_carry(v)));                       // reduce the < 24p value directly
+      gstore(out + go, ntt_store_plain(v));                               // reduce the < 30p value directly
       continue;
     } else if (P.post == 4) {
       w = tab_load(postA + k);                                            // (ginv^N1)^k; minv * ginv^k1 sits in the folded inter-pass table
     } else {
       w = post_c;                                                         // minv (ifft, domain.rs:163-173)
     }
-    const FrU prod = tw_mul(v, w);                                         // v < 30p, limbs < 4*2^29: < 2p
-    gstore(out + go, u_to_std_lt2p(prod));
+    const FrU prod = ntt_post_mul(v, w);                                   // v < 30p, limbs < 4*2^29: < 2p
+    gstore(out + go, ntt_reduce_lt2p(prod));
   }
 }
 
@@ -393,7 +356,7 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_wl_kernel(const Fr* __re
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   static_assert(LOG_NP >= 8, "full tiles of rows of at least 256 elements");
   constexpr uint32_t np = 1u << LOG_NP;
-  constexpr uint32_t SKIP_MAX = LOG_NP > 10 ? 1 : 2;   // as in ntt_pass_kernel
+  using SCH = NttSchedule<LOG_NP>;                      // as in ntt_pass_kernel
   constexpr uint32_t pitch = np;
   constexpr uint32_t plane = 0;                         // (element-major tiles only)
   const uint32_t G = P.g, log_g = 31u - (uint32_t)__clz(G);
@@ -423,30 +386,17 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_wl_kernel(const Fr* __re
   auto at = [&](uint32_t x) __attribute__((always_inline)) { return row + (swz_wl(x) ^ rx); };
 
   auto fetch = [&](uint64_t gi, uint32_t x) __attribute__((always_inline)) {           // element x of a row from memory: < 2p, N
-    FrU v = u_from_std(gload(in + gi));
-    if (P.pre == 4) v = tw_mul(v, tab_load(preB + (gi - (uint64_t)x * P.in_xs)));     // transforms without a full table: g^col (a first pass: gi = x * S + col)
+    FrU v = ntt_load(gload(in + gi));
+    if (P.pre == 4) v = ntt_pre4(v, tab_load(preB + (gi - (uint64_t)x * P.in_xs)));   // transforms without a full table: g^col (a first pass: gi = x * S + col)
     if (P.pre == 1) {                                   // distribute_powers (domain.rs:176-189)
-      v = tw_mul(v, tab_load(preA + (gi >> P.pre_h)));
-      v = tw_mul(v, tab_load(preB + (gi & ((1ull << P.pre_h) - 1))));
+      v = ntt_pre1(v, tab_load(preA + (gi >> P.pre_h)), [&] { return tab_load(preB + (gi & ((1ull << P.pre_h) - 1))); });
     } else if (P.pre == 2) {
-      v = tw_mul(v, tab_load(preA + x));                // folded tables: (g^S)^x here, g^col in the inter-pass table
+      v = ntt_pre2(v, tab_load(preA + x));              // folded tables: (g^S)^x here, g^col in the inter-pass table
     }
     return v;
   };
-  // (the butterfly of ntt_pass_kernel, bounds noted there)
-  auto bf = [&](auto stc, FrU& u, FrU& t, const TwU& w, bool skip) __attribute__((always_inline)) {
-    constexpr uint32_t ST = (uint32_t) decltype(stc)::value;
-    if (!skip) t = tw_mul(t, w);
-    else t = u_carry(t);
-    FrU sum = u_add(u, t);
-    if constexpr ((ST & 3) == 3) sum = u_carry(sum);
-    FrU dif;
-    if constexpr (ST == 1) dif = skip ? u_sub<4, 1>(u, t) : u_sub<2, 1>(u, t);
-    else if constexpr (ST == 2) dif = skip ? u_sub<8, 1>(u, t) : u_sub<2, 1>(u, t);
-    else dif = u_sub<2, 1>(u, t);
-    u = sum;
-    t = dif;
-  };
+  // (the butterfly of ntt_pass_kernel: ntt_bf)
+  const auto bf = ntt_bf_fn<SCH>();
   // element k of row g leaves the tile: the closing product (inter-pass twiddle, or the post scale) and the store
   auto emit = [&](uint32_t k, const FrU& v_in) __attribute__((always_inline)) {
     FrU v = v_in;                                       // < 30p, limbs < 4*2^29
@@ -456,24 +406,23 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_wl_kernel(const Fr* __re
       w = tab_load(twF + go);
     } else if (P.tw_mul != 0) {
       const uint64_t ex = P.tw_mul * k * (lo * G + g);
-      v = tw_mul(v, tab_load(twA + (ex >> P.tw_h)));
+      v = ntt_post_mul(v, tab_load(twA + (ex >> P.tw_h)));
       w = tab_load(twB + (ex & ((1ull << P.tw_h) - 1)));
     } else if (P.post == 2) {
-      v = tw_mul(v, tab_load(postA + (go >> P.post_h)));
-      v = tw_mul(v, tab_load(postB + (go & ((1ull << P.post_h) - 1))));
+      v = ntt_post_mul2(v, tab_load(postA + (go >> P.post_h)), [&] { return tab_load(postB + (go & ((1ull << P.post_h) - 1))); });
       w = post_c;
     } else if (P.post == 3) {
-      gstore(out + go, u_to_std_lt32p(u_carry(v)));
+      gstore(out + go, ntt_store_plain(v));
       return;
     } else if (P.post == 4) {
       w = tab_load(postA + k);
     } else if (P.post == 5) {                           // transforms without a full table: (minv * ginv^(row's first output index)) * (ginv^stride)^k
-      v = tw_mul(v, tab_load(postB + (go - (uint64_t)k * P.out_xs)));
+      v = ntt_post_mul(v, tab_load(postB + (go - (uint64_t)k * P.out_xs)));
       w = tab_load(postA + k);
     } else {
       w = post_c;
     }
-    gstore(out + go, u_to_std_lt2p(tw_mul(v, w)));
+    gstore(out + go, ntt_store_mul(v, w));
   };
 
   constexpr uint32_t S0 = LOG_NP & 1;
@@ -499,8 +448,8 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_wl_kernel(const Fr* __re
       a = lds_load(lds, plane, at(x0)); b = lds_load(lds, plane, at(x0 + 1)); c = lds_load(lds, plane, at(x0 + 2)); d = lds_load(lds, plane, at(x0 + 3));
       TwU w0{a, a};
       if (twisted) w0 = tab_load(stage_tab + 1);
-      bf(std::integral_constant<int, 0>{}, a, b, w0, !twisted);
-      bf(std::integral_constant<int, 0>{}, c, d, w0, !twisted);
+      [[clang::always_inline]] bf(std::integral_constant<int, 0>{}, a, b, w0, !twisted);
+      [[clang::always_inline]] bf(std::integral_constant<int, 0>{}, c, d, w0, !twisted);
       lds_store(lds, plane, at(x0), a); lds_store(lds, plane, at(x0 + 1), b); lds_store(lds, plane, at(x0 + 2), c); lds_store(lds, plane, at(x0 + 3), d);
       // pair 1 takes groups of 8 elements = two of these lanes' quadruples: inside the wave while it owns >= 8 elements per row
       if (8u <= own) wave_handover(); else __syncthreads();
@@ -513,22 +462,22 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_wl_kernel(const Fr* __re
     const uint32_t j = qf & (m - 1), x0 = ((qf >> s) << (s + 2)) + j;
     const uint32_t ia = at(x0), ib = at(x0 + m), ic = at(x0 + 2 * m), id = at(x0 + 3 * m);
     if (!(first && direct)) { a = lds_load(lds, plane, ia); b = lds_load(lds, plane, ib); c = lds_load(lds, plane, ic); d = lds_load(lds, plane, id); }
-    const bool one = !twisted && s <= SKIP_MAX && j == 0;
+    const bool one = !twisted && SCH::may_skip(s) && j == 0;
     {
       TwU w1{a, a};
       if (!one) w1 = tab_load(stage_tab + (twisted ? m + j : j << (LOG_NP - 1 - s)));   // (requesting it before the hand-over, to run under the wait: measured, nothing)
-      bf(std::integral_constant<int, (int)s>{}, a, b, w1, one);
-      bf(std::integral_constant<int, (int)s>{}, c, d, w1, one);
+      [[clang::always_inline]] bf(std::integral_constant<int, (int)s>{}, a, b, w1, one);
+      [[clang::always_inline]] bf(std::integral_constant<int, (int)s>{}, c, d, w1, one);
     }
-    const bool one2 = !twisted && s + 1 <= SKIP_MAX && j == 0;
+    const bool one2 = !twisted && SCH::may_skip(s + 1) && j == 0;
     {
       TwU w2{a, a};
       if (!one2) w2 = tab_load(stage_tab + (twisted ? 2u * m + j : j << (LOG_NP - 2 - s)));
-      bf(std::integral_constant<int, (int)s + 1>{}, a, c, w2, one2);
+      [[clang::always_inline]] bf(std::integral_constant<int, (int)s + 1>{}, a, c, w2, one2);
     }
     {
       const TwU w3 = tab_load(stage_tab + (twisted ? 3u * m + j : (j + m) << (LOG_NP - 2 - s)));
-      bf(std::integral_constant<int, (int)s + 1>{}, b, d, w3, false);
+      [[clang::always_inline]] bf(std::integral_constant<int, (int)s + 1>{}, b, d, w3, false);
     }
     if constexpr (!last) {
       lds_store(lds, plane, ia, a); lds_store(lds, plane, ib, b); lds_store(lds, plane, ic, c); lds_store(lds, plane, id, d);
@@ -561,8 +510,8 @@ __global__ void ntt_full_twiddle_kernel(UTab* __restrict__ full, const UTab* __r
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
   const uint64_t k = i >> log_s, col = i & ((1ull << log_s) - 1), ex = k * col;
-  const FrU w = tw_mul(tab_load(A + (ex >> h)).w, tab_load(B + (ex & ((1ull << h) - 1))));  // < 2p, N
-  tab_store(full + i, tw_make(u_to_std_lt2p(w)));                                           // canonical, and its quotient
+  const FrU w = ntt_tab_product(tab_load(A + (ex >> h)), tab_load(B + (ex & ((1ull << h) - 1))));   // < 2p, N
+  tab_store(full + i, ntt_tab_entry(w));                                                    // canonical, and its quotient
 }
 
 // (round 5) The same table with the scale factors of a coset / inverse transform FOLDED in:
@@ -579,11 +528,11 @@ __global__ void ntt_full_folded_kernel(UTab* __restrict__ full, const UTab* __re
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
   const uint64_t k = i >> log_s, col = i & ((1ull << log_s) - 1), ex = k * col;
-  FrU w = tw_mul(tab_load(A + (ex >> h)).w, tab_load(B + (ex & ((1ull << h) - 1))));        // < 2p, N (and so after every product below)
-  if (preA != nullptr) w = tw_mul(tw_mul(w, tab_load(preA + (col >> pre_h))), tab_load(preB + (col & ((1ull << pre_h) - 1))));
-  if (postA != nullptr) w = tw_mul(tw_mul(w, tab_load(postA + (k >> post_h))), tab_load(postB + (k & ((1ull << post_h) - 1))));
-  if (has_post_c) w = tw_mul(w, post_c);
-  tab_store(full + i, tw_make(u_to_std_lt2p(w)));
+  FrU w = ntt_tab_product(tab_load(A + (ex >> h)), tab_load(B + (ex & ((1ull << h) - 1))));   // < 2p, N (and so after every product below)
+  if (preA != nullptr) w = ntt_tab_factor2(w, tab_load(preA + (col >> pre_h)), [&] { return tab_load(preB + (col & ((1ull << pre_h) - 1))); });
+  if (postA != nullptr) w = ntt_tab_factor2(w, tab_load(postA + (k >> post_h)), [&] { return tab_load(postB + (k & ((1ull << post_h) - 1))); });
+  if (has_post_c) w = ntt_tab_factor(w, post_c);
+  tab_store(full + i, ntt_tab_entry(w));
 }
 
 // (round 5) The row twist (pre^S)^x of a coset transform's first pass folded into the butterflies: a DIT block of 2m = 2^(s+1) outputs at
@@ -604,10 +553,9 @@ __global__ void ntt_stage_table_kernel(UTab* tab, Fr pre, uint64_t s_cols, Fr om
 __global__ void ntt_scale_kernel(Fr* a, uint64_t n, Fr c, const UTab* __restrict__ gA, const UTab* __restrict__ gB, uint32_t h) {
   uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  FrU v = u_from_std(gload(a + i));
-  v = u_mul(v, u_mul(u_from_std(c), UPow2<FrParams, 266>::get()));      // (c is a Montgomery form: c * 2^261, then the Montgomery product) < 2p
-  if (gA != nullptr) v = tw_mul(tw_mul(v, tab_load(gA + (i >> h))), tab_load(gB + (i & ((1ull << h) - 1))));
-  gstore(a + i, u_to_std_lt2p(v));
+  FrU v = ntt_scale_const(ntt_load(gload(a + i)), c);                   // (c is a Montgomery form: c * 2^261, then the Montgomery product) < 2p
+  if (gA != nullptr) v = ntt_scale_pow(v, tab_load(gA + (i >> h)), [&] { return tab_load(gB + (i & ((1ull << h) - 1))); });
+  gstore(a + i, ntt_reduce_lt2p(v));
 }
 
 }  // namespace

@@ -8,7 +8,7 @@
 //           limb as a number (a product, a shift, a mask, the conversion to a column term) reports it if lo < 0 or hi >= 2^32:
 //           "limb expression can wrap".  So limbs 0..7 of a lazy subtraction are judged where u_carry or a product reads them.
 //   IvAcc   a 64-bit column sum with [lo, hi] on 128 bits; `+=` reports hi >= 2^64: "column sum can exceed 2^64".
-//   value   every FpU carries vb: value < vb * p (UValueBound).  The hooks of fieldu.hpp (UChk) set it by the RESULT lines stated there
+//   value   every FpU carries vb: value < vb * p (UValueBound), infinite ("unknown") until some hook sets it.  The hooks of fieldu.hpp (UChk) set it by the RESULT lines stated there
 //           (u_mul: < a b / 2^261 + p; u_sub: < a + K p; ...) and test the stated PRECONDITIONS against what the caller passed.
 //   limb 8  is correlated with the value: u_sub lets it wrap in u32 arithmetic until the carry, so its interval may reach below zero and
 //           is not judged there.  It is judged through the value bound: after the carry the element is N-form and its value is
@@ -17,8 +17,9 @@
 //           un-carried difference (u_sub_lazy) keeps the plain interval a.l[8] + (K p >> 232) - S - b.l[8]: if that can be negative, the
 //           product that reads it reports it.
 #pragma once
-#define ZK_U_BOUNDS_CHECK 1
+#define ZK_U_BOUNDS_CHECK 2   // 2: UChk has the hooks of u_mul_shoup, u_mul3 / u_mul4 and u_from_std (fieldu.hpp: UChk2)
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <string>
@@ -145,7 +146,8 @@ inline IvLimb::IvLimb(const IvAcc& a) : v((uint32_t)a.v), lo(0), hi(0xffffffffll
 using ulimb_t = IvLimb;
 using uacc_t = IvAcc;
 struct UValueBound {
-  double vb = 0;  // value < vb * p
+  double vb = INFINITY;  // value < vb * p.  UNKNOWN (infinity) until a hook of the producing function states a bound: an element made by a
+                         // function without a result hook fails the next precondition that reads its value, instead of passing as "< 0 p"
 };
 
 template <class PR>
@@ -212,6 +214,39 @@ struct UChk {
   }
   template <class PR> static void mul(FpU<PR>& r, const FpU<PR>& a, const FpU<PR>& b) { mont_result(r, a.vb * b.vb); }
   template <class PR> static void mul(FpU<PR>& r, const FpU<PR>& a, const FpU<PR>& b, const FpU<PR>& c, const FpU<PR>& d) { mont_result(r, a.vb * b.vb + c.vb * d.vb); }
+  template <class PR, class... R> static void muln_pre(const FpU<PR>& a, const R&... rest) {
+    if (!n_form(a)) say("u_mul3 / u_mul4 precondition: an operand is not N-form (max limb " + std::to_string(max_limb(a, "u_mul3 / u_mul4")) + ")");
+    if constexpr (sizeof...(R) > 0) muln_pre(rest...);
+  }
+  template <class PR> static void muln(FpU<PR>& r, const FpU<PR>& a, const FpU<PR>& b, const FpU<PR>& c, const FpU<PR>& d, const FpU<PR>& e, const FpU<PR>& f) {
+    mont_result(r, a.vb * b.vb + c.vb * d.vb + e.vb * f.vb);
+  }
+  template <class PR> static void muln(FpU<PR>& r, const FpU<PR>& a, const FpU<PR>& b, const FpU<PR>& c, const FpU<PR>& d, const FpU<PR>& e, const FpU<PR>& f,
+                                      const FpU<PR>& g, const FpU<PR>& h) {
+    mont_result(r, a.vb * b.vb + c.vb * d.vb + e.vb * f.vb + g.vb * h.vb);
+  }
+  // u_mul_shoup, exactly as stated at the function: w canonical in N-form, wq N-form with top limb < 2^29, limbs of a < 2^31, value(a) < 160 p
+  template <class PR> static void shoup_pre(const FpU<PR>& a, const FpU<PR>& w, const FpU<PR>& wq) {
+    if (!n_form(w) || !(w.vb <= 1 + EPS)) say("u_mul_shoup precondition: w is not a canonical N-form constant (value < " + std::to_string(w.vb) + " p)");
+    for (int i = 0; i < 9; ++i)
+      if (wq.l[i].lo < 0 || wq.l[i].hi >= (1 << 29)) { say("u_mul_shoup precondition: wq is not N-form with a top limb below 2^29"); break; }
+    for (int i = 0; i < 9; ++i)
+      if (a.l[i].lo < 0 || a.l[i].hi >= (int64_t(1) << 31)) {
+        say("u_mul_shoup precondition: limb " + std::to_string(i) + " of a lies in [" + std::to_string(a.l[i].lo) + ", " + std::to_string(a.l[i].hi) + "], not in [0, 2^31)");
+        break;
+      }
+    if (!(a.vb <= 160 + EPS)) say("u_mul_shoup precondition: value(a) < " + std::to_string(a.vb) + " p is not within 160 p");
+  }
+  template <class PR> static void shoup(FpU<PR>& r, const FpU<PR>&) {
+    r.vb = 2;
+    for (int i = 0; i < 8; ++i)
+      if (r.l[i].lo < 0 || r.l[i].hi >= (1 << 29)) say("Shoup result: not N-form");
+    const int64_t t = top_of<PR>(2);      // N-form and 0 <= value < 2p: limb 8 = value >> 232
+    if ((int64_t)r.l[8].v > t) say("the model's value bound does not hold for the concrete run (Shoup result)");
+    r.l[8].lo = 0, r.l[8].hi = t, r.l[8].wide = false;
+  }
+  // the memory format holds canonical elements (include/mi355zk.h): the re-packed value is < p
+  template <class PR> static void from_std(FpU<PR>& r) { r.vb = 1; }
   template <int K, int S, class PR> static void sub_pre(const FpU<PR>& a, const FpU<PR>& b) {
     for (int i = 0; i < 8; ++i) {
       if (b.l[i].lo < 0 || b.l[i].hi >= (int64_t)S << 29) say("u_sub<" + std::to_string(K) + ", " + std::to_string(S) + "> precondition: limb " + std::to_string(i) + " of b reaches " + std::to_string(b.l[i].hi) + ", not below S * 2^29");
