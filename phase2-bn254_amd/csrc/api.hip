@@ -317,8 +317,7 @@ void mi355zk_shutdown(void) {
     DeviceGuard guard;
     prof_release_all();
     ntt_release_all();
-    exp_scratch_release_all();
-    mul_slots_release_all();
+    scalar_mul_release_all();
     host_entry_release_all();
     msm_release_g1();
     msm_release_g2();

@@ -86,8 +86,7 @@ int exp_scratch(size_t bytes, void* stream, void** out);
 extern std::mutex g_exp_launch_mu;
 int batch_normalize_g1(void* d_io_affine, const void* d_z, uint64_t n, hipStream_t st);
 int batch_normalize_g2(void* d_io_affine, const void* d_z, uint64_t n, hipStream_t st);
-void exp_scratch_release_all();
-void mul_slots_release_all();
+void scalar_mul_release_all();   // the scratch above and batch_mul's slot rings
 
 // records.hip: base vectors in the CALLER's record layout (bellman's `G1Affine { x, y, infinity: bool }` is 72 B, G2Affine 136 B).
 // stride == 0 is the packed layout of the group (64 / 128 B, x || y, no flag).  Every non-packed layout passed below has been checked by

@@ -19,6 +19,7 @@
 
 #include "../../include/mi355zk.h"
 #include "curve.hpp"
+#include "device_mem.hpp"
 #include "device_util.hpp"
 
 namespace zk {
@@ -283,18 +284,15 @@ template <class DecodeLaunch>
 int run_decode(size_t n, hipStream_t st, long long* err_index, DecodeLaunch&& launch) {
   if (err_index) *err_index = -1;
   if (n == 0) return ZK_OK;
-  unsigned long long* d_err = nullptr;
-  ZK_HIP(hipMalloc(&d_err, 8));
-  hipError_t e = hipMemsetAsync(d_err, 0xff, 8, st);
+  DevTemp err;
+  if (int rc = err.alloc(8)) return rc;
+  unsigned long long* d_err = err.as<unsigned long long>();
   unsigned long long h_err = ~0ull;
-  if (e == hipSuccess) {
-    launch(d_err);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(&h_err, d_err, 8, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  (void)hipFree(d_err);
-  ZK_HIP(e);
+  ZK_HIP(hipMemsetAsync(d_err, 0xff, 8, st));
+  launch(d_err);
+  ZK_HIP(hipGetLastError());
+  ZK_HIP(hipMemcpyAsync(&h_err, d_err, 8, hipMemcpyDeviceToHost, st));
+  ZK_HIP(hipStreamSynchronize(st));  // the decode is done with d_err: it dies with this call
   if (h_err == ~0ull) return ZK_OK;
   if (err_index) *err_index = (long long)(h_err >> 8);
   return (int)(h_err & 0xff);

@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "../../include/mi355zk.h"
+#include "device_mem.hpp"
 #include "window_mul.hpp"
 
 namespace zk {
@@ -102,22 +103,19 @@ int ubench(uint32_t blocks, uint32_t iters, const uint64_t* a_raw, const uint64_
   Fp<PR> a, b;
   std::memcpy(&a, a_raw, 32);
   std::memcpy(&b, b_raw, 32);
-  Fp<PR>* d_out = nullptr;
-  ZK_HIP(hipMalloc(&d_out, 8 * sizeof(Fp<PR>)));
-  hipEvent_t e0, e1;
-  ZK_HIP(hipEventCreate(&e0));
-  ZK_HIP(hipEventCreate(&e1));
+  DevTemp out;
+  if (int rc = out.alloc(8 * sizeof(Fp<PR>))) return rc;
+  Fp<PR>* d_out = out.as<Fp<PR>>();
+  Events ev(2, hipEventDefault);  // (with timing)
+  ZK_HIP(ev.create());
   hipLaunchKernelGGL(fp_mul_ubench_kernel<PR>, dim3(blocks), dim3(256), 0, 0, a, b, iters, d_out);  // warm-up
   ZK_HIP(hipDeviceSynchronize());
-  ZK_HIP(hipEventRecord(e0, 0));
+  ZK_HIP(hipEventRecord(ev[0], 0));
   hipLaunchKernelGGL(fp_mul_ubench_kernel<PR>, dim3(blocks), dim3(256), 0, 0, a, b, iters, d_out);
-  ZK_HIP(hipEventRecord(e1, 0));
-  ZK_HIP(hipEventSynchronize(e1));
-  ZK_HIP(hipEventElapsedTime(ms, e0, e1));
-  ZK_HIP(hipMemcpy(out_raw, d_out, 4 * sizeof(Fp<PR>), hipMemcpyDeviceToHost));
-  ZK_HIP(hipFree(d_out));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
+  ZK_HIP(hipEventRecord(ev[1], 0));
+  ZK_HIP(hipEventSynchronize(ev[1]));
+  ZK_HIP(hipEventElapsedTime(ms, ev[0], ev[1]));
+  ZK_HIP(hipMemcpy(out_raw, d_out, 4 * sizeof(Fp<PR>), hipMemcpyDeviceToHost));  // synchronous on the null stream: nothing uses d_out after it
   return ZK_OK;
 }
 

@@ -17,6 +17,7 @@
 #include "fixed_base.hpp"
 
 #include "api_internal.hpp"
+#include "device_mem.hpp"
 
 namespace zk {
 namespace {
@@ -146,17 +147,15 @@ int table_build(void* d_table, size_t table_bytes, const uint64_t* base_raw, voi
   for (int w = 0; w < FB_WINDOWS; ++w)
     for (int j = 1; j <= FB_HALF; ++j) table_scalar(w, j, &ks[((size_t)w * FB_HALF + (j - 1)) * 8]);
   hipStream_t st = (hipStream_t)stream;
-  void* d_in = nullptr;                                     // the base, then the scalars (one-time work: a plain allocation)
+  // the base, then the scalars (one-time work: a plain allocation).  Declared AFTER `base` and `ks`: on an early error exit its free, which
+  DevTemp in;  // waits for the device, runs before those sources of the queued copies die
   const size_t base_bytes = (sizeof(Affine<F>) + 255) & ~(size_t)255;
-  ZK_HIP(hipMalloc(&d_in, base_bytes + ks.size() * 4));
-  int rc = ZK_OK;
-  if (hipMemcpyAsync(d_in, &base, sizeof base, hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync((char*)d_in + base_bytes, ks.data(), ks.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess)
-    rc = ZK_ERR_DEVICE;
-  if (rc == ZK_OK) rc = batch_exp<F>(d_table, d_in, 1, (char*)d_in + base_bytes, 0, (size_t)FB_ENTRIES, stream, nullptr, false, /*g2_trusted=*/true);
-  if (hipStreamSynchronize(st) != hipSuccess && rc == ZK_OK) rc = ZK_ERR_DEVICE;
-  (void)hipFree(d_in);
-  return rc;
+  if (int rc = in.alloc(base_bytes + ks.size() * 4)) return rc;
+  ZK_HIP(hipMemcpyAsync(in.p, &base, sizeof base, hipMemcpyHostToDevice, st));
+  ZK_HIP(hipMemcpyAsync(in.as<char>(base_bytes), ks.data(), ks.size() * 4, hipMemcpyHostToDevice, st));
+  const int rc = batch_exp<F>(d_table, in.p, 1, in.as<char>(base_bytes), 0, (size_t)FB_ENTRIES, stream, nullptr, false, /*g2_trusted=*/true);
+  // the copies out of `base` and `ks` and the build are done with `in`: all three die with this call
+  return hipStreamSynchronize(st) != hipSuccess && rc == ZK_OK ? ZK_ERR_DEVICE : rc;
 }
 
 template <class G>
@@ -232,19 +231,16 @@ int bases_build(void* d_tables, size_t table_bytes, const uint64_t* bases_raw, s
     for (size_t e = 0; e < (size_t)FB_ENTRIES; ++e) index[b * FB_ENTRIES + e] = (uint32_t)b;
   }
   hipStream_t st = (hipStream_t)stream;
-  void* d_in = nullptr;                                     // the bases, the scalars, the base index (one-time work: a plain allocation)
+  DevTemp in;  // the bases, the scalars, the base index (one-time work: a plain allocation); declared AFTER the host vectors, as in table_build
   const size_t bases_bytes = (n_bases * sizeof(G1Affine) + 255) & ~(size_t)255, ks_bytes = total * 32;
-  ZK_HIP(hipMalloc(&d_in, bases_bytes + ks_bytes + total * 4));
-  char* d = (char*)d_in;
-  int rc = ZK_OK;
-  if (hipMemcpyAsync(d, bases.data(), n_bases * sizeof(G1Affine), hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(d + bases_bytes, ks.data(), ks_bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(d + bases_bytes + ks_bytes, index.data(), total * 4, hipMemcpyHostToDevice, st) != hipSuccess)
-    rc = ZK_ERR_DEVICE;
-  if (rc == ZK_OK) rc = batch_exp<Fq>(d_tables, d, 0, d + bases_bytes, 0, total, stream, (const uint32_t*)(d + bases_bytes + ks_bytes));
-  if (hipStreamSynchronize(st) != hipSuccess && rc == ZK_OK) rc = ZK_ERR_DEVICE;
-  (void)hipFree(d_in);
-  return rc;
+  if (int rc = in.alloc(bases_bytes + ks_bytes + total * 4)) return rc;
+  char* d = in.as<char>();
+  ZK_HIP(hipMemcpyAsync(d, bases.data(), n_bases * sizeof(G1Affine), hipMemcpyHostToDevice, st));
+  ZK_HIP(hipMemcpyAsync(d + bases_bytes, ks.data(), ks_bytes, hipMemcpyHostToDevice, st));
+  ZK_HIP(hipMemcpyAsync(d + bases_bytes + ks_bytes, index.data(), total * 4, hipMemcpyHostToDevice, st));
+  const int rc = batch_exp<Fq>(d_tables, d, 0, d + bases_bytes, 0, total, stream, (const uint32_t*)(d + bases_bytes + ks_bytes));
+  // the copies out of the host vectors and the build are done with `in`: they all die with this call
+  return hipStreamSynchronize(st) != hipSuccess && rc == ZK_OK ? ZK_ERR_DEVICE : rc;
 }
 
 int bases_lincomb(void* d_out, const void* d_tables, size_t n_bases, const void* d_first, const void* d_scalars, size_t n, size_t slice_len,

@@ -49,7 +49,7 @@ int msm_dev_entry(const void* d_bases, size_t n_bases, size_t base_offset, const
     size_t words = (n + 31) / 32;
     rc = density_lease.acquire(dev, words * 8, st);
     if (rc) return rc;
-    d_density = (uint32_t*)density_lease.b->p;
+    d_density = (uint32_t*)density_lease.p();
     d_prefix = d_density + words;
     ZK_HIP(hipMemcpyAsync(d_density, density, words * 4, hipMemcpyHostToDevice, st));
     ZK_HIP(hipMemcpyAsync(d_prefix, P.prefix.data(), words * 4, hipMemcpyHostToDevice, st));

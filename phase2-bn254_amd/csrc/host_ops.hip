@@ -273,38 +273,33 @@ int sparse_matvec(void* d_out, const void* d_bases, size_t n_bases, const uint32
   // reference's either way.  (2^20 bases, 2.9 M terms: 156 -> ~155 ms general coefficients, 90 -> ~61 ms with 90 % unit coefficients.)
   const bool by_member = std::is_same<F, Fq2>::value && !g2_trusted && nnz >= 2 * n_bases && n_bases > 0;
   const size_t terms_bytes = ((nnz ? nnz : 1) * sizeof(Affine<F>) + 255) & ~(size_t)255;
-  Affine<F>* d_terms = nullptr;
-  const bool own = d_scratch == nullptr || scratch_bytes < terms_bytes + 256 + (by_member ? n_bases : 0);
-  if (own) ZK_HIP(hipMalloc(&d_terms, terms_bytes + 256 + (by_member ? n_bases : 0)));
-  else d_terms = (Affine<F>*)d_scratch;
+  DevTemp own;  // (used when the caller brought no scratch, or too little)
+  const size_t need = terms_bytes + 256 + (by_member ? n_bases : 0);
+  if (d_scratch == nullptr || scratch_bytes < need) {
+    if (int rc = own.alloc(need)) return rc;
+    d_scratch = own.p;
+  }
+  Affine<F>* d_terms = (Affine<F>*)d_scratch;
   uint8_t* d_member = by_member ? reinterpret_cast<uint8_t*>(d_terms) + terms_bytes + 256 : nullptr;
   {
     // the ABI cannot trust the index arrays: an out-of-range column would be an out-of-bounds gather in batch_exp
     uint32_t* d_flag = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(d_terms) + terms_bytes);
     uint32_t h_flag = 0;
-    hipError_t e = hipMemsetAsync(d_flag, 0, 4, (hipStream_t)stream);
-    if (e == hipSuccess) {
-      const uint64_t work = nnz > n_rows + 1 ? nnz : n_rows + 1;
-      hipLaunchKernelGGL(csr_check_kernel, dim3((unsigned)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096)), dim3(256), 0, (hipStream_t)stream,
-                         d_row_ptr, d_col, (uint64_t)n_rows, (uint64_t)nnz, (uint64_t)n_bases, d_flag);
-      e = hipMemcpyAsync(&h_flag, d_flag, 4, hipMemcpyDeviceToHost, (hipStream_t)stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess || h_flag) {
-      if (own) (void)hipFree(d_terms);
-      if (e != hipSuccess) ZK_HIP(e);
-      return ZK_ERR_BAD_ARGS;
-    }
+    ZK_HIP(hipMemsetAsync(d_flag, 0, 4, (hipStream_t)stream));
+    const uint64_t work = nnz > n_rows + 1 ? nnz : n_rows + 1;
+    hipLaunchKernelGGL(csr_check_kernel, dim3((unsigned)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096)), dim3(256), 0, (hipStream_t)stream,
+                       d_row_ptr, d_col, (uint64_t)n_rows, (uint64_t)nnz, (uint64_t)n_bases, d_flag);
+    ZK_HIP(hipMemcpyAsync(&h_flag, d_flag, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    ZK_HIP(hipStreamSynchronize((hipStream_t)stream));
+    if (h_flag) return ZK_ERR_BAD_ARGS;
   }
-  int rc = ZK_OK;
   if constexpr (std::is_same<F, Fq2>::value)
-    if (by_member) rc = g2_subgroup_flags(d_bases, n_bases, stream, d_member);
-  if (rc == ZK_OK) rc = batch_exp<F>(d_terms, d_bases, 0, d_coeffs, 0, nnz, stream, d_col, /*shortcut_unit_scalars=*/true, g2_trusted, d_member);
-  if (rc == ZK_OK)
-    rc = group == 1 ? segsum_g1_device(d_terms, nnz, d_row_ptr, (uint32_t)n_rows, (hipStream_t)stream, d_out)
+    if (by_member)
+      if (int rc = g2_subgroup_flags(d_bases, n_bases, stream, d_member)) return rc;
+  if (int rc = batch_exp<F>(d_terms, d_bases, 0, d_coeffs, 0, nnz, stream, d_col, /*shortcut_unit_scalars=*/true, g2_trusted, d_member)) return rc;
+  // the segmented sum synchronises the stream before it returns (msm_host.hpp: segsum_device): nothing queued reads `own` when it dies
+  return group == 1 ? segsum_g1_device(d_terms, nnz, d_row_ptr, (uint32_t)n_rows, (hipStream_t)stream, d_out)
                     : segsum_g2_device(d_terms, nnz, d_row_ptr, (uint32_t)n_rows, (hipStream_t)stream, d_out);
-  if (own) (void)hipFree(d_terms);
-  return rc;
 }
 
 // The QAP evaluation on HOST buffers, over the device set (SURVEY 8f row 3 for a single-process caller: MPCParameters::new over a

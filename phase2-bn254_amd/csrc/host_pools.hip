@@ -7,29 +7,9 @@
 #include "bases_cache.hpp"
 
 namespace zk {
-std::mutex g_stage_mu;
-static std::vector<HostStage*> g_stages;  // the pool: as many stages as there have been concurrent host-buffer calls
-HostStage* host_stage(int dev) {  // an idle stage of the device, marked busy (nullptr: no streams to be had)
-  HostStage* mine = nullptr;
-  {
-    std::lock_guard<std::mutex> lk(g_stage_mu);
-    for (HostStage* s : g_stages)  // the idle stage of this device with the largest staging buffers
-      if (!s->busy && s->dev == dev && (mine == nullptr || s->sc[0].bytes + s->sc[1].bytes > mine->sc[0].bytes + mine->sc[1].bytes)) mine = s;
-    if (mine) mine->busy = true;
-  }
-  if (mine == nullptr) {
-    mine = new HostStage();
-    mine->dev = dev;
-    mine->busy = true;
-    if (hipStreamCreateWithFlags(&mine->copy, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&mine->compute, hipStreamNonBlocking) != hipSuccess) {
-      delete mine;
-      return nullptr;
-    }
-    std::lock_guard<std::mutex> lk(g_stage_mu);
-    g_stages.push_back(mine);
-  }
-  return mine;
+SlotPool<HostStage>& stage_pool() {  // as many stages as there have been concurrent host-buffer calls (CallLease::open leases them)
+  static SlotPool<HostStage> pool;
+  return pool;
 }
 
 static std::mutex g_devset_mu;
@@ -61,15 +41,9 @@ unsigned devset_turn() { return g_devset_turn.fetch_add(1); }
 
 void host_entry_release_all() {
   bases_cache_release_all();
-  std::lock_guard<std::mutex> lk(g_stage_mu);
-  for (HostStage* s : g_stages) {
-    (void)hipSetDevice(s->dev);
-    for (DevBuf* b : {&s->sc[0], &s->sc[1], &s->bases, &s->raw}) b->release();
-  }
-  std::lock_guard<std::mutex> dl(DeviceBufPool::mu());
-  for (DeviceBufPool::Buf* b : DeviceBufPool::all()) {
-    (void)hipSetDevice(b->dev);
-    b->release();
-  }
+  stage_pool().release_all([](HostStage& s) {  // (the streams stay: they hold no device memory)
+    for (DevBuf* b : {&s.sc[0], &s.sc[1], &s.bases, &s.raw}) b->release();
+  });
+  DeviceBufPool::pool().release_all([](DeviceBufPool::Buf& b) { b.release(); });
 }
 }  // namespace zk

@@ -280,13 +280,13 @@ int msm_finish_set(const MsmCall<F>& A, SmallWsLease& lease, std::unique_lock<st
   prof_end(msm_slots().red, st);
   if (msm_checkpoint(A, "reduce", P.chunks[0])) return (int)ZK_ERR_DEVICE;
 
-  ZK_HIP(hipMemcpyAsync(pin.b->p, A.ws.wsums, back_bytes, hipMemcpyDeviceToHost, st));
+  ZK_HIP(hipMemcpyAsync(pin.slot->p, A.ws.wsums, back_bytes, hipMemcpyDeviceToHost, st));
   // (parking on an event recorded in front of the reduction and polling the stream from there was measured in round 4: 1.790 against
   // 1.805 ms at 2^20, nothing at 2^12 .. 2^22 or for the prover's eight threads -- the runtime's own wait is not what a short call waits for)
   ZK_HIP(hipStreamSynchronize(st));
-  const XYZZ<F>* h_wsums = reinterpret_cast<const XYZZ<F>*>(pin.b->p);
+  const XYZZ<F>* h_wsums = reinterpret_cast<const XYZZ<F>*>(pin.slot->p);
   unsigned long long h_errs[2];
-  std::memcpy(h_errs, (const char*)pin.b->p + (back_bytes - 16), 16);
+  std::memcpy(h_errs, (const char*)pin.slot->p + (back_bytes - 16), 16);
   lease.idle = true;
   const auto t_join0 = std::chrono::steady_clock::now();
   unsigned long long h_err = h_errs[0];
@@ -297,9 +297,9 @@ int msm_finish_set(const MsmCall<F>& A, SmallWsLease& lease, std::unique_lock<st
     hipLaunchKernelGGL(msm_identity_scan_kernel<F>, dim3((unsigned)((A.n + 255) / 256)), dim3(256), 0, st, d_bases, d_sc_first, A.n, A.base_offset, A.d_density,
                        A.d_dprefix, A.ws.d_err);
     ZK_HIP(hipGetLastError());
-    ZK_HIP(hipMemcpyAsync(pin.b->p, A.ws.d_err, 8, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipMemcpyAsync(pin.slot->p, A.ws.d_err, 8, hipMemcpyDeviceToHost, st));
     ZK_HIP(hipStreamSynchronize(st));
-    std::memcpy(&h_err, pin.b->p, 8);
+    std::memcpy(&h_err, pin.slot->p, 8);
     lease.idle = true;
   }
   // the device is done with the workspace: let the next multiexp (another host thread -- the prover keeps 8 in
@@ -404,7 +404,8 @@ int msm_device(const Affine<F>* d_bases, uint64_t n_bases, uint64_t base_offset,
     rc = tws_acquire(dev, P.L.total_bytes, st, &lease, &base);
   } else {
     lk.lock();
-    rc = ws_reserve(dev_ws, P.L.total_bytes, &base);
+    rc = dev_ws.buf.reserve(P.L.total_bytes);
+    base = dev_ws.buf.p;
   }
   if (rc) return rc;
   const MsmCall<F> A{{P, K, R.group, dev, st, n, base_offset, table_stride, d_density, d_dprefix, scalars_mont}, MsmWs<F>((char*)base, P.L), dense};
@@ -469,10 +470,9 @@ int segsum_device(const Affine<F>* d_points, uint64_t nnz, const uint32_t* d_row
   size_t o_buckets = take((size_t)n_rows * sizeof(XYZZ<F>));
   Workspace& dev_ws = ws_of(dev);
   std::lock_guard<std::mutex> lk(dev_ws.mu);
-  void* base = nullptr;
-  int rc = ws_reserve(dev_ws, off, &base);
+  int rc = dev_ws.buf.reserve(off);
   if (rc) return rc;
-  char* ws = (char*)base;
+  char* ws = (char*)dev_ws.buf.p;
   uint32_t* vals = (uint32_t*)(ws + o_vals);
   uint32_t* size_hist = (uint32_t*)(ws + o_hist);
   uint32_t* sizes_b = (uint32_t*)(ws + o_sizes_b);

@@ -11,6 +11,7 @@
 #include <utility>
 #include <vector>
 
+#include "device_mem.hpp"
 #include "device_util.hpp"
 #include "ntt_plan.hpp"
 
@@ -259,46 +260,11 @@ int build_folded(hipStream_t st, uint32_t log_n, const Fr& omega, PowTables* T, 
   return 0;
 }
 
-struct ScratchBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
-// one scratch array per (device, stream): calls on one stream are ordered by the stream itself, calls on
-// different streams must not share a buffer.  Guarded by g_run_mu (held only while launching).
-std::map<std::pair<int, hipStream_t>, ScratchBuf> g_scratch;
+// The inter-pass scratch, one array per (device, stream) and bounded (device_mem.hpp: StreamScratch).  Guarded by g_run_mu, which every
+// transform holds while launching: that keeps other transforms from being enqueued while the scratch drops a device's buffers.
+StreamScratch g_scratch;
 std::mutex g_run_mu;
-
-// The scratch of (dev, st), at least `bytes` long.  One buffer per stream a caller has ever used: bounded -- a caller that makes a
-// stream per call must not pin a buffer per stream for ever.  Past 16 streams on this device everything is dropped once the device is
-// idle; g_run_mu, held by the caller, keeps other transforms from being enqueued meanwhile.
-constexpr size_t NTT_SCRATCH_STREAMS_MAX = 16;
-int scratch_for(int dev, hipStream_t st, size_t bytes, Fr** out) {
-  if (g_scratch.find(std::make_pair(dev, st)) == g_scratch.end()) {
-    size_t mine = 0;
-    for (auto& kv : g_scratch) mine += kv.first.first == dev ? 1 : 0;
-    if (mine >= NTT_SCRATCH_STREAMS_MAX) {
-      ZK_HIP(hipDeviceSynchronize());
-      for (auto it = g_scratch.begin(); it != g_scratch.end();) {
-        if (it->first.first != dev) { ++it; continue; }
-        (void)hipFree(it->second.p);
-        it = g_scratch.erase(it);
-      }
-    }
-  }
-  ScratchBuf& sb = g_scratch[std::make_pair(dev, st)];
-  if (sb.bytes < bytes) {
-    if (sb.p) {
-      ZK_HIP(hipStreamSynchronize(st));  // earlier passes on this stream may still read the old buffer
-      ZK_HIP(hipFree(sb.p));
-    }
-    sb.p = nullptr;
-    sb.bytes = 0;
-    ZK_HIP(hipMalloc(&sb.p, bytes));
-    sb.bytes = bytes;
-  }
-  *out = (Fr*)sb.p;
-  return ZK_OK;
-}
+int scratch_for(int dev, hipStream_t st, size_t bytes, Fr** out) { return g_scratch.get(dev, st, bytes, (void**)out); }
 
 // host: a Montgomery form -> the plain integer and its quotient.  The quotient is a 261-round division (~10 us on the host): the few
 // scale factors a process uses (1/m per domain size) are kept.  Called under g_run_mu.
@@ -322,11 +288,7 @@ void ntt_release_all() {
     kv.second.free_all();
   }
   g_tables.clear();
-  for (auto& kv : g_scratch) {
-    (void)hipSetDevice(kv.first.first);
-    (void)hipFree(kv.second.p);
-  }
-  g_scratch.clear();
+  g_scratch.release_all();
 }
 
 }  // namespace zk

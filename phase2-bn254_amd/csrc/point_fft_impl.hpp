@@ -24,6 +24,7 @@
 #include <cstdlib>
 
 #include "../../include/mi355zk.h"
+#include "device_mem.hpp"
 #include "window_mul.hpp"
 
 namespace zk {
@@ -155,14 +156,14 @@ int point_fft(void* d_points, uint32_t log_n, const Fr& omega, bool scale, const
   const uint64_t lanes_max = scale ? n : (n >= 2 ? n / 2 : 1);
   const uint64_t limit = pfft_lanes_per_launch(G::PFFT_LANES);
   const uint64_t chunk = lanes_max < limit ? lanes_max : limit;  // table: 8 entries per lane
-  char* buf = nullptr;
   const size_t o_work = 0, o_tw = o_work + ((n * sizeof(WorkPt<G>) + 255) & ~(size_t)255), o_z = o_tw + (((n / 2 + 1) * 32 + 255) & ~(size_t)255),
                o_tab = o_z + ((n * sizeof(typename G::Z) + 255) & ~(size_t)255), total = o_tab + 8 * chunk * sizeof(Tab);
-  ZK_HIP(hipMalloc(&buf, total));
-  WorkPt<G>* work = (WorkPt<G>*)(buf + o_work);
-  uint32_t* tw = (uint32_t*)(buf + o_tw);
-  typename G::Z* zbuf = (typename G::Z*)(buf + o_z);
-  Tab* tab = (Tab*)(buf + o_tab);
+  DevTemp buf;
+  if (int rc = buf.alloc(total)) return rc;
+  WorkPt<G>* work = buf.as<WorkPt<G>>(o_work);
+  uint32_t* tw = buf.as<uint32_t>(o_tw);
+  typename G::Z* zbuf = buf.as<typename G::Z>(o_z);
+  Tab* tab = buf.as<Tab>(o_tab);
   auto stage = [&](uint32_t s, uint64_t b0, uint64_t m, int mode, const Fr& c) {
     const dim3 grid((unsigned)((m + 255) / 256)), block(256);
     if (G::ENDO_EVERYWHERE || split) hipLaunchKernelGGL((pfft_stage_kernel<G, true>), grid, block, 0, st, work, tw, log_n, s, b0, m, tab, mode, c);
@@ -175,11 +176,9 @@ int point_fft(void* d_points, uint32_t log_n, const Fr& omega, bool scale, const
   if (scale)
     for (uint64_t b0 = 0; b0 < n; b0 += chunk) stage(0u, b0, n - b0 < chunk ? n - b0 : chunk, 1, scale_canon);
   hipLaunchKernelGGL(pfft_store_kernel<G>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, work, (typename G::Aff*)d_points, zbuf, log_n);
-  hipError_t e = hipGetLastError();
-  int rc = e == hipSuccess ? normalize(d_points, zbuf, n, st) : ZK_ERR_DEVICE;
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  (void)hipFree(buf);
-  ZK_HIP(e);
+  ZK_HIP(hipGetLastError());
+  const int rc = normalize(d_points, zbuf, n, st);
+  ZK_HIP(hipStreamSynchronize(st));  // every stage and the normalisation are done with buf: it dies with this call
   return rc;
 }
 

@@ -13,6 +13,7 @@
 
 #include "../../include/mi355zk.h"
 #include "field.hpp"
+#include "device_mem.hpp"
 #include "device_util.hpp"
 
 #ifndef R1CS_SHORT_ROW_MAX
@@ -153,21 +154,18 @@ int mi355zk_bn254_fr_sparse_matvec_check_dev(const uint32_t* d_row_ptr, const ui
   return zk::abi_guard([&]() -> int {
     if (int rc = zk::csr_args(d_row_ptr, d_col, d_coeff_id, n_coeffs, n_x, n_rows, nnz)) return rc;
     if (!d_row_ptr) return nnz == 0 ? ZK_OK : ZK_ERR_BAD_ARGS;   // (no rows: nothing to hold a term)
-    // once per matrix and synchronous by contract: a flag word of its own (hipFree waits for the device, which this call does anyway)
-    uint32_t* d_bad = nullptr;
+    // once per matrix and synchronous by contract: a flag word of its own (its free waits for the device, which this call does anyway)
+    zk::DevTemp flag;
+    if (int rc = flag.alloc(sizeof(uint32_t))) return rc;
+    uint32_t* d_bad = flag.as<uint32_t>();
     uint32_t bad = 1;
-    ZK_HIP(hipMalloc((void**)&d_bad, sizeof bad));
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(d_bad, 0, sizeof bad, st);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(zk::fr_sparse_matvec_check_kernel, dim3(zk::capped_blocks(n_rows > nnz ? n_rows : nnz)), dim3(256), 0, st, d_row_ptr, d_col,
-                         d_coeff_id, (uint32_t)n_coeffs, (uint32_t)n_x, (uint32_t)n_rows, (uint32_t)nnz, d_bad);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(d_bad);
-    ZK_HIP(e);
+    ZK_HIP(hipMemsetAsync(d_bad, 0, sizeof bad, st));
+    hipLaunchKernelGGL(zk::fr_sparse_matvec_check_kernel, dim3(zk::capped_blocks(n_rows > nnz ? n_rows : nnz)), dim3(256), 0, st, d_row_ptr, d_col,
+                       d_coeff_id, (uint32_t)n_coeffs, (uint32_t)n_x, (uint32_t)n_rows, (uint32_t)nnz, d_bad);
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipStreamSynchronize(st));  // the check is done with d_bad: it dies with this call
     return bad ? ZK_ERR_BAD_ARGS : ZK_OK;
   });
 }

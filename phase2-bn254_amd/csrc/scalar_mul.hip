@@ -22,6 +22,7 @@
 #include "window_mul.hpp"
 
 #include "api_internal.hpp"
+#include "device_mem.hpp"
 
 namespace zk {
 // ------------------------------------------------------------------------------------------------
@@ -383,53 +384,17 @@ int batch_normalize_g2(void* d_io_affine, const void* d_z, uint64_t n, hipStream
   return ZK_OK;
 }
 
-// per (device, stream) scratch for the Z coordinates between the two kernels (grow-only; freed at shutdown)
-struct ExpScratch {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
+// per (device, stream) scratch for the Z coordinates between the two kernels (device_mem.hpp: StreamScratch; freed at shutdown).  Under
+// g_exp_mu; the callers hold g_exp_launch_mu from here until their kernels are enqueued, so no other scalar-multiplication kernels are
+// being enqueued while the scratch drops a device's buffers.
 static std::mutex g_exp_mu;
-static std::map<std::pair<int, void*>, ExpScratch> g_exp_scratch;
+static StreamScratch g_exp_scratch;
 
 int exp_scratch(size_t bytes, void* stream, void** out) {
   int dev = 0;
   ZK_HIP(hipGetDevice(&dev));
   std::lock_guard<std::mutex> lk(g_exp_mu);
-  // (one buffer per stream a caller has ever used: bounded.  Past 16 streams on this device everything is dropped once the device
-  // is idle -- the callers hold g_exp_launch_mu, so no other scalar-multiplication kernels are being enqueued meanwhile.)
-  if (g_exp_scratch.find(std::make_pair(dev, stream)) == g_exp_scratch.end()) {
-    size_t mine = 0;
-    for (auto& kv : g_exp_scratch) mine += kv.first.first == dev ? 1 : 0;
-    if (mine >= 16) {
-      ZK_HIP(hipDeviceSynchronize());
-      for (auto it = g_exp_scratch.begin(); it != g_exp_scratch.end();) {
-        if (it->first.first != dev) { ++it; continue; }
-        (void)hipFree(it->second.p);
-        it = g_exp_scratch.erase(it);
-      }
-    }
-  }
-  ExpScratch& sb = g_exp_scratch[std::make_pair(dev, stream)];
-  if (sb.bytes < bytes) {
-    if (sb.p) {
-      ZK_HIP(hipStreamSynchronize((hipStream_t)stream));  // earlier launches on this stream may still use the old buffer
-      ZK_HIP(hipFree(sb.p));
-    }
-    sb.p = nullptr;
-    sb.bytes = 0;
-    ZK_HIP(hipMalloc(&sb.p, bytes));
-    sb.bytes = bytes;
-  }
-  *out = sb.p;
-  return ZK_OK;
-}
-void exp_scratch_release_all() {
-  std::lock_guard<std::mutex> lk(g_exp_mu);
-  for (auto& kv : g_exp_scratch) {
-    (void)hipSetDevice(kv.first.first);
-    (void)hipFree(kv.second.p);
-  }
-  g_exp_scratch.clear();
+  return g_exp_scratch.get(dev, (hipStream_t)stream, bytes, out);
 }
 
 // QAP coefficients are mostly +-1 (circom R1CS): a term with coefficient 1 / r - 1 / 0 is the base itself / its negative (where the
@@ -686,9 +651,11 @@ int g2_subgroup_check(const void* d_points, size_t n, void* stream, long long* b
 // per-(device, stream) ring of slots allocated once: hipMalloc / hipFree per call synchronise the whole device, and this entry is
 // the building block of per-point batch_exp synthesis (256 calls per bench input).  A slot is in flight only until its call's
 // closing stream synchronisation; MUL_SLOTS concurrent calls on ONE stream is more than any caller here issues.
+// NOT bounded like the scratch above: 4 KiB per (device, stream) ever used, kept until shutdown.  Dropping rings past a bound would need
+// g_exp_launch_mu held from the slot to the enqueue of the call that reads it.
 constexpr int MUL_SLOTS = 16;
 struct MulSlots {
-  void* p = nullptr;
+  DevBuf ring;
   unsigned next = 0;
 };
 static std::mutex g_mul_mu;
@@ -698,15 +665,19 @@ static int mul_slot(void* stream, void** out) {
   ZK_HIP(hipGetDevice(&dev));
   std::lock_guard<std::mutex> lk(g_mul_mu);
   MulSlots& m = g_mul_slots[std::make_pair(dev, stream)];
-  if (m.p == nullptr) ZK_HIP(hipMalloc(&m.p, (size_t)MUL_SLOTS * 256));
-  *out = (char*)m.p + (size_t)(m.next++ % MUL_SLOTS) * 256;
+  if (int rc = m.ring.reserve((size_t)MUL_SLOTS * 256)) return rc;
+  *out = (char*)m.ring.p + (size_t)(m.next++ % MUL_SLOTS) * 256;
   return ZK_OK;
 }
-void mul_slots_release_all() {
+void scalar_mul_release_all() {  // the scratch and the slot rings (mi355zk_shutdown)
+  {
+    std::lock_guard<std::mutex> lk(g_exp_mu);
+    g_exp_scratch.release_all();
+  }
   std::lock_guard<std::mutex> lk(g_mul_mu);
   for (auto& kv : g_mul_slots) {
     (void)hipSetDevice(kv.first.first);
-    (void)hipFree(kv.second.p);
+    kv.second.ring.release();
   }
   g_mul_slots.clear();
 }

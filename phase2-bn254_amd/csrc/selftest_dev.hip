@@ -5,6 +5,8 @@
 #define ZK_ST_CHAIN 0
 #include "selftest_dev_ops.hpp"
 
+#include "device_mem.hpp"
+
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -13,11 +15,6 @@ namespace zk {
 int selftest_dev_launch_chain(int op, int which, const uint32_t* d_in, uint32_t* d_out, uint32_t blocks);   // selftest_dev_chain.hip
 
 namespace {
-struct DevBuf {   // freed on every exit
-  uint32_t* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
 int selftest_dev_op(int op_flags, int which, const uint32_t* in, size_t in_words, uint32_t* out, size_t out_words, size_t n) {
   const bool chain = (op_flags & MI355ZK_DEVOP_CHAIN) != 0;
   const int op = op_flags & ~MI355ZK_DEVOP_CHAIN;
@@ -34,13 +31,14 @@ int selftest_dev_op(int op_flags, int which, const uint32_t* in, size_t in_words
   std::vector<uint32_t> h_out(n_pad * out_words);
   // a test hook: plain allocations, the null stream and a device synchronise on the calling thread's CURRENT device -- not the library's
   // device set, pools or streams, which it neither uses nor disturbs
-  DevBuf d_in, d_out;
-  ZK_HIP(hipMalloc(&d_in.p, h_in.size() * sizeof(uint32_t)));
-  ZK_HIP(hipMalloc(&d_out.p, h_out.size() * sizeof(uint32_t)));
+  DevTemp d_in, d_out;   // freed on every exit
+  if (int rc = d_in.alloc(h_in.size() * sizeof(uint32_t))) return rc;
+  if (int rc = d_out.alloc(h_out.size() * sizeof(uint32_t))) return rc;
   ZK_HIP(hipMemcpy(d_in.p, h_in.data(), h_in.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   ZK_HIP(hipMemset(d_out.p, 0xA5, h_out.size() * sizeof(uint32_t)));   // a result that is never written does not read as zero
   const uint32_t blocks = (uint32_t)(n_pad / 256);
-  const int rc = chain ? selftest_dev_launch_chain(op, which, d_in.p, d_out.p, blocks) : selftest_plain::devop_launch(op, which, d_in.p, d_out.p, blocks);
+  const int rc = chain ? selftest_dev_launch_chain(op, which, d_in.as<uint32_t>(), d_out.as<uint32_t>(), blocks)
+                       : selftest_plain::devop_launch(op, which, d_in.as<uint32_t>(), d_out.as<uint32_t>(), blocks);
   if (rc != ZK_OK) return rc;
   ZK_HIP(hipDeviceSynchronize());
   ZK_HIP(hipMemcpy(h_out.data(), d_out.p, h_out.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
