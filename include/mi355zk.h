@@ -263,6 +263,32 @@ int mi355zk_bn254_g1_msm_table_dev(const void *d_table, size_t n_bases, size_t b
                                    const uint32_t *density, size_t density_bits, uint32_t flags, void *stream, uint64_t out_xyz[12]);
 int mi355zk_bn254_g2_msm_table_dev(const void *d_table, size_t n_bases, size_t base_offset, const void *d_scalars, size_t n_scalars,
                                    const uint32_t *density, size_t density_bits, uint32_t flags, void *stream, uint64_t out_xyz[24]);
+/* ---- BATCHED MULTIEXP: n_vectors exponent vectors against ONE base vector and ONE density map -- the shape of "many proofs over one
+ * groth16::Parameters" (bellman/tests/mimc.rs:260-341 proves in a loop over one CRS; h / l / a / b_g1 / b_g2 and the density maps belong
+ * to the circuit, the exponents to the witness).  Replaces a loop of n_vectors calls of mi355zk_bn254_g{1,2}_msm_ex_dev(..., flags, 1, 0,
+ * ...): the vectors run as n_vectors x n_windows windows of one pipeline -- one launch sequence and one copy back -- which is what a
+ * short multiexp (below ~2^18 exponents it does not fill the device) is made of.  Vector v is the n_scalars exponents at d_scalars +
+ * v * scalar_stride * 32 bytes (`scalar_stride` in scalars, >= n_scalars; what lies between two vectors is not read); `base_offset`,
+ * `density` and `flags` (MI355ZK_MSM_SCALARS_MONTGOMERY) as in msm_ex_dev, shared by all vectors.  out_xyz takes n_vectors Jacobian
+ * points (12 / 24 words each).
+ * ERRORS are per vector: rcs[v] and err_indices[v] are the return code and mi355zk_last_error_index() of the single call on vector v
+ * (0 / -1: its point is in out_xyz; otherwise its words are untouched), whatever the other vectors hold: a pipeline pass that meets an
+ * identity base under a non-zero exponent or a non-canonical exponent is discarded and its vectors are evaluated one by one, and so is
+ * every vector when n_scalars reaches beyond the bases (UnexpectedEof).  Those are caller bugs; only the clean batch is fast.
+ * The RETURN VALUE is 0 when the call ran (then rcs / err_indices are valid); 3 when it is refused as a whole, before any device work --
+ * a NULL out_xyz / rcs / err_indices (or bases / scalars with a non-zero count), n_vectors == 0, scalar_stride < n_scalars, a size
+ * >= 2^31, an unknown flag -- or the device code (-1).  n_vectors == 1 is msm_ex_dev(..., 1, 0, ...); n_scalars == 0 gives n_vectors
+ * identities.  No window tables, window groups or host buffers here; a batch too large for one pass (4096 bucket sets, or the
+ * workspace budget for long vectors) runs several passes inside the call.
+ * msm_batch_geometry (diagnostic): the bucket sets one pass may hold, the windows of one vector of n_scalars exponents and the vectors
+ * per pass the call above would take for (n_scalars, n_vectors); group 1 = G1, 2 = G2; any pointer may be NULL. */
+int mi355zk_bn254_g1_msm_batch_dev(const void *d_bases, size_t n_bases, size_t base_offset, const void *d_scalars, size_t n_scalars,
+                                   size_t scalar_stride, size_t n_vectors, const uint32_t *density, size_t density_bits, uint32_t flags,
+                                   void *stream, uint64_t *out_xyz /* n_vectors x 12 */, int *rcs, long long *err_indices);
+int mi355zk_bn254_g2_msm_batch_dev(const void *d_bases, size_t n_bases, size_t base_offset, const void *d_scalars, size_t n_scalars,
+                                   size_t scalar_stride, size_t n_vectors, const uint32_t *density, size_t density_bits, uint32_t flags,
+                                   void *stream, uint64_t *out_xyz /* n_vectors x 24 */, int *rcs, long long *err_indices);
+int mi355zk_msm_batch_geometry(size_t n_scalars, size_t n_vectors, int group, uint32_t *max_windows, uint32_t *n_windows, uint32_t *vectors_per_pass);
 /* exponent index at which the last failing multiexp of this thread raised its error, or -1 */
 long long mi355zk_last_error_index(void);
 /* bits of the bucket field (c for the power-of-two window layouts, ceil(log2(B/2 + 1)) for the mixed-radix ones) and

@@ -86,6 +86,9 @@ extern "C" {
     pub fn mi355zk_bn254_g2_msm_table_build_dev(d_bases: *const c_void, n_bases: usize, d_table: *mut c_void, table_bytes: usize, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_g1_msm_table_dev(d_table: *const c_void, n_bases: usize, base_offset: usize, d_scalars: *const c_void, n_scalars: usize, density: *const u32, density_bits: usize, flags: u32, stream: *mut c_void, out_xyz: *mut u64 /* [12] */) -> c_int;
     pub fn mi355zk_bn254_g2_msm_table_dev(d_table: *const c_void, n_bases: usize, base_offset: usize, d_scalars: *const c_void, n_scalars: usize, density: *const u32, density_bits: usize, flags: u32, stream: *mut c_void, out_xyz: *mut u64 /* [24] */) -> c_int;
+    pub fn mi355zk_bn254_g1_msm_batch_dev(d_bases: *const c_void, n_bases: usize, base_offset: usize, d_scalars: *const c_void, n_scalars: usize, scalar_stride: usize, n_vectors: usize, density: *const u32, density_bits: usize, flags: u32, stream: *mut c_void, out_xyz: *mut u64, rcs: *mut c_int, err_indices: *mut c_longlong) -> c_int;
+    pub fn mi355zk_bn254_g2_msm_batch_dev(d_bases: *const c_void, n_bases: usize, base_offset: usize, d_scalars: *const c_void, n_scalars: usize, scalar_stride: usize, n_vectors: usize, density: *const u32, density_bits: usize, flags: u32, stream: *mut c_void, out_xyz: *mut u64, rcs: *mut c_int, err_indices: *mut c_longlong) -> c_int;
+    pub fn mi355zk_msm_batch_geometry(n_scalars: usize, n_vectors: usize, group: c_int, max_windows: *mut u32, n_windows: *mut u32, vectors_per_pass: *mut u32) -> c_int;
     pub fn mi355zk_last_error_index() -> c_longlong;
     pub fn mi355zk_msm_window_bits(n_scalars: usize, n_windows: *mut c_int) -> c_int;
     pub fn mi355zk_msm_window_bits_groups(n_scalars: usize, window_groups: u32, n_windows: *mut c_int) -> c_int;

@@ -13,7 +13,8 @@ Layout:
                   compute_constrained, verify_transform_constrained (file to file, mmap'ed; the in-memory flows of verify.py are the yardstick);
                   prepare_phase2_plan, prepare_phase2_files (a response -> every phase1radix2m{k}, one vector on the device at a time),
                   read_phase1radix2m_file, points_load / points_store (wire records in a mapping <-> a device vector)
-  prover.py       the caller of the path: groth16 create_proof (prover.rs:202-343) over the device library
+  prover.py       the caller of the path: groth16 create_proof (prover.rs:202-343) over the device library; create_proofs: many
+                  witnesses of one circuit, each of the eight multiexps one batched call (bellman.multiexp_many)
   ceremony.py     the ceremony-side callers (batch_exp, merge_pairs, QAP evaluation, point FFT, codecs, file containers)
   bellman.py      host-side mirror of the reference's interface for this path:
                   multiexp(), FullDensity, DensityTracker, EvaluationDomain, SynthesisError
@@ -33,6 +34,7 @@ from .bellman import (  # noqa: F401
     Worker,
     h_poly_host,
     multiexp,
+    multiexp_many,
     pin_bases,
     unpin_bases,
 )

@@ -361,6 +361,57 @@ def multiexp(pool: Worker, bases, density_map, exponents, window_group=None, sca
     return _Ready(error=DeviceError(f"mi355zk device failure rc={rc}"))
 
 
+def multiexp_many(pool: Worker, bases, density_map, exponents, scalars_montgomery: bool = False) -> list:
+    """B multiexps over ONE base vector and ONE density map in one call (mi355zk_bn254_g{1,2}_msm_batch_dev): the shape of "many proofs
+    over one Parameters".  `exponents`: a contiguous (B, n, 4) int64 device tensor, vector v = exponents[v]; `bases` = (tensor, offset)
+    or (MsmTable, offset) -- a table's window 0 is the vector itself (msm_table_build_dev), so the batch runs over table[:n_bases].
+    Returns B ready futures; future v carries what multiexp(pool, bases, density_map, exponents[v], ...) would: the Jacobian limbs, or
+    the same SynthesisError / ValueError / DeviceError."""
+    import torch
+
+    arr, offset = bases
+    assert _is_torch(exponents) and exponents.is_cuda and exponents.is_contiguous() and exponents.dim() == 3 and exponents.shape[2] == 4
+    n_vec, n_exp = int(exponents.shape[0]), int(exponents.shape[1])
+    qs = density_map.get_query_size()
+    if qs is not None:
+        assert qs == n_exp  # multiexp.rs:347-352
+    words, dbits = density_map.words()
+    if isinstance(arr, MsmTable):
+        dev_bases, n_bases, limbs = arr.table, arr.n_bases, arr.limbs
+    else:
+        assert _is_torch(arr) and arr.is_cuda and arr.is_contiguous()
+        dev_bases, n_bases, limbs = arr, int(arr.shape[0]), int(arr.shape[1])
+    group = {8: 1, 16: 2}[limbs]
+    if n_vec == 0:
+        return []
+    lib = _lib.load()
+    out = np.zeros((n_vec, 12 * group), dtype=np.uint64)
+    rcs = np.zeros(n_vec, dtype=np.int32)
+    idxs = np.full(n_vec, -1, dtype=np.int64)
+    fn = lib.mi355zk_bn254_g1_msm_batch_dev if group == 1 else lib.mi355zk_bn254_g2_msm_batch_dev
+    with torch.cuda.device(dev_bases.device):
+        rc = fn(C.c_void_p(dev_bases.data_ptr()), n_bases, offset, C.c_void_p(exponents.data_ptr()), n_exp, n_exp, n_vec,
+                words.ctypes.data_as(C.c_void_p) if words is not None else None, dbits,
+                _lib.MSM_SCALARS_MONTGOMERY if scalars_montgomery else 0, _stream_ptr(), out.ctypes.data_as(C.c_void_p),
+                rcs.ctypes.data_as(C.c_void_p), idxs.ctypes.data_as(C.c_void_p))
+    if rc != _lib.OK:   # the call as a whole: every vector carries it
+        rcs[:] = rc
+
+    def ready(v):
+        code, idx = int(rcs[v]), int(idxs[v])
+        if code == _lib.OK:
+            return _Ready(out[v].copy())
+        if code == _lib.ERR_UNEXPECTED_IDENTITY:
+            return _Ready(error=SynthesisError(SynthesisError.UNEXPECTED_IDENTITY, idx))
+        if code == _lib.ERR_UNEXPECTED_EOF:
+            return _Ready(error=SynthesisError(SynthesisError.IO_UNEXPECTED_EOF, idx))
+        if code == _lib.ERR_BAD_ARGS:
+            return _Ready(error=ValueError("mi355zk: bad arguments"))
+        return _Ready(error=DeviceError(f"mi355zk device failure rc={code}"))
+
+    return [ready(v) for v in range(n_vec)]
+
+
 class EvaluationDomain:
     """bellman/src/domain.rs:30-203 for G = Scalar<Bn256>: coefficients are (m, 4) u64 Montgomery Fr
     limbs, either a numpy array or a torch CUDA tensor (int64 view)."""

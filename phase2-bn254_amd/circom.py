@@ -444,3 +444,20 @@ def prove(pool, circuit: CircomCircuit, params, r: int, s: int, compiled: Compil
             raise ValueError("`compiled` was not compiled from this circuit (variable or constraint counts differ)")
         assignment = prepare_prover_dev(compiled, circuit.witness)
     return _prover.create_proof(pool, _prover.Parameters(vk, p["h"], p["l"], p["a"], p["b_g1"], p["b_g2"]), assignment, r, s)
+
+
+def prove_many(pool, circuit: CircomCircuit, params, witnesses, rs, ss, compiled: CompiledCircuit = None):
+    """prove for many witnesses of one circuit: prepare_prover_dev per witness over ONE CompiledCircuit (compiled here when the caller
+    brings none), then prover.create_proofs -- every multiexp of the batch in one pipeline.  witnesses: what prepare_prover_dev takes,
+    one per proof; rs, ss: the blinding scalars, one pair per proof.  Returns [(a, b, c)]: what prove returns for each witness."""
+    from . import prover as _prover
+
+    p = filter_params(params)
+    host = lambda t: t.cpu().numpy().view(np.uint64).reshape(-1)  # noqa: E731
+    vk = {k: host(p["vk"][k]) for k in ("alpha_g1", "beta_g1", "delta_g1", "beta_g2", "delta_g2")}
+    if compiled is None:
+        compiled = compile_circuit(circuit, p["h"].device)
+    if (compiled.num_inputs, compiled.num_aux, compiled.n) != (circuit.num_inputs, circuit.num_aux, len(circuit.constraints) + circuit.num_inputs):
+        raise ValueError("`compiled` was not compiled from this circuit (variable or constraint counts differ)")
+    assignments = [prepare_prover_dev(compiled, w) for w in witnesses]
+    return _prover.create_proofs(pool, _prover.Parameters(vk, p["h"], p["l"], p["a"], p["b_g1"], p["b_g2"]), assignments, rs, ss)

@@ -441,6 +441,35 @@ int mi355zk_bn254_g2_msm_ex_dev(const void* d_bases, size_t n_bases, size_t base
     return msm_dev_entry<2>(d_bases, n_bases, base_offset, d_scalars, n_scalars, density, density_bits, stream, out_xyz, window_groups, window_group, flags);
   });
 }
+// B exponent vectors over one base vector and one density map in one pipeline
+int mi355zk_bn254_g1_msm_batch_dev(const void* d_bases, size_t n_bases, size_t base_offset, const void* d_scalars, size_t n_scalars, size_t scalar_stride,
+                                   size_t n_vectors, const uint32_t* density, size_t density_bits, uint32_t flags, void* stream, uint64_t* out_xyz, int* rcs,
+                                   long long* err_indices) {
+  return abi_guard([&]() -> int {
+    return msm_batch_dev_entry<1>(d_bases, n_bases, base_offset, d_scalars, n_scalars, scalar_stride, n_vectors, density, density_bits, flags, stream, out_xyz, rcs,
+                                  err_indices);
+  });
+}
+int mi355zk_bn254_g2_msm_batch_dev(const void* d_bases, size_t n_bases, size_t base_offset, const void* d_scalars, size_t n_scalars, size_t scalar_stride,
+                                   size_t n_vectors, const uint32_t* density, size_t density_bits, uint32_t flags, void* stream, uint64_t* out_xyz, int* rcs,
+                                   long long* err_indices) {
+  return abi_guard([&]() -> int {
+    return msm_batch_dev_entry<2>(d_bases, n_bases, base_offset, d_scalars, n_scalars, scalar_stride, n_vectors, density, density_bits, flags, stream, out_xyz, rcs,
+                                  err_indices);
+  });
+}
+// the bucket sets one pipeline pass of a batch may hold, and the vectors per pass msm_batch_dev runs for (n_scalars, n_vectors) (diagnostic)
+int mi355zk_msm_batch_geometry(size_t n_scalars, size_t n_vectors, int group, uint32_t* max_windows, uint32_t* n_windows, uint32_t* vectors_per_pass) {
+  return abi_guard([&]() -> int {
+    if ((group != 1 && group != 2) || n_scalars >= (1ull << 31) || n_vectors >= (1ull << 31)) return ZK_ERR_BAD_ARGS;
+    uint32_t W = 0, per = 0, cap = 0;
+    msm_batch_geometry(n_scalars ? n_scalars : 1, (uint32_t)n_vectors, group, &cap, &W, &per);
+    if (max_windows) *max_windows = cap;
+    if (n_windows) *n_windows = W;
+    if (vectors_per_pass) *vectors_per_pass = per;
+    return ZK_OK;
+  });
+}
 int mi355zk_msm_table_geometry(size_t n_bases, int group, uint32_t* window_bits, uint32_t* n_windows) {
   return abi_guard([&]() -> int {
     if ((group != 1 && group != 2) || n_bases >= (1ull << 31)) return ZK_ERR_BAD_ARGS;

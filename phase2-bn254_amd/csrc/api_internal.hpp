@@ -39,6 +39,13 @@ void msm_table_geometry(uint64_t n_bases, int group, uint32_t* c, uint32_t* W, u
 int msm_g2_device(const void* d_bases, uint64_t n_bases, uint64_t base_offset, const void* d_scalars, uint64_t n, const uint32_t* d_density,
                   const uint32_t* d_dprefix, hipStream_t st, uint64_t out_xyz[24], long long* err_index, uint32_t wgroups, uint32_t wgroup, bool scalars_mont,
                   MsmChunks* chunks, uint64_t table_stride = 0, uint32_t table_c = 0);
+// n_vectors exponent vectors over one base vector and one density map in one pipeline (msm_host.hpp: msm_device_batch); per-vector codes in rcs / err_indices
+int msm_g1_batch_device(const void* d_bases, uint64_t n_bases, uint64_t base_offset, const void* d_scalars, uint64_t n, uint64_t scalar_stride,
+                        uint32_t n_vectors, const uint32_t* d_density, const uint32_t* d_dprefix, hipStream_t st, uint64_t* out_xyz, int* rcs,
+                        long long* err_indices, bool scalars_mont);
+int msm_g2_batch_device(const void* d_bases, uint64_t n_bases, uint64_t base_offset, const void* d_scalars, uint64_t n, uint64_t scalar_stride,
+                        uint32_t n_vectors, const uint32_t* d_density, const uint32_t* d_dprefix, hipStream_t st, uint64_t* out_xyz, int* rcs,
+                        long long* err_indices, bool scalars_mont);
 int msm_g1_dense_device(const void* d_bases, const void* d_bases2, const void* d_scalars, uint64_t n, hipStream_t st, uint64_t* out_xyz, uint64_t* out2_xyz);
 int msm_g1_buckets_device(const void* d_bases, const void* d_scalars, uint64_t n, hipStream_t st, uint64_t out_xyz[12], uint32_t* n_buckets, uint32_t* n_vals,
                           uint32_t* first, uint32_t* last, size_t cap_buckets, uint32_t* vals, size_t cap_vals, uint64_t* records);
@@ -48,6 +55,7 @@ int segsum_g2_device(const void* d_points, uint64_t nnz, const uint32_t* d_row_p
 void msm_release_g1();
 void msm_release_g2();
 void msm_geometry(uint64_t n, uint32_t wgroups, uint32_t* c, uint32_t* W);
+void msm_batch_geometry(uint64_t n, uint32_t n_vectors, int group, uint32_t* max_windows, uint32_t* W, uint32_t* vectors_per_pass);   // MSM_BATCH_MAX_WINDOWS, windows of one vector, msm_batch_split
 int msm_selftest_digits(uint64_t n, uint32_t wgroups, const uint32_t scalar[8], uint32_t w_start, uint32_t w_stop, int direct, int32_t* digits,
                         uint32_t* geom);
 // point_fft.hip
@@ -128,6 +136,13 @@ template <int GROUP>
 int msm_dev_entry(const void* d_bases, size_t n_bases, size_t base_offset, const void* d_scalars, size_t n_scalars, const uint32_t* density,
                   size_t density_bits, void* stream, uint64_t* out_xyz, uint32_t wgroups = 1, uint32_t wgroup = 0, uint32_t flags = 0,
                   MsmChunks* chunks = nullptr, bool table = false);
+// the batch entry (mi355zk_bn254_g{1,2}_msm_batch_dev): vector v's rc / exponent index as msm_dev_entry gives them for that vector alone
+template <int GROUP>
+int msm_batch_dev_entry(const void* d_bases, size_t n_bases, size_t base_offset, const void* d_scalars, size_t n_scalars, size_t scalar_stride,
+                        size_t n_vectors, const uint32_t* density, size_t density_bits, uint32_t flags, void* stream, uint64_t* out_xyz, int* rcs,
+                        long long* err_indices);
+extern template int msm_batch_dev_entry<1>(const void*, size_t, size_t, const void*, size_t, size_t, size_t, const uint32_t*, size_t, uint32_t, void*, uint64_t*, int*, long long*);
+extern template int msm_batch_dev_entry<2>(const void*, size_t, size_t, const void*, size_t, size_t, size_t, const uint32_t*, size_t, uint32_t, void*, uint64_t*, int*, long long*);
 // host buffers: whole on one device (streamed upload, pinned-bases cache) or cut into cells over the device set of mi355zk_init
 template <int GROUP>
 int msm_host_entry(const uint8_t* bases, size_t n_bases, size_t base_offset, const uint64_t* scalars, size_t n_scalars, const uint32_t* density,

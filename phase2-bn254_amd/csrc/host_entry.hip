@@ -75,6 +75,55 @@ int msm_dev_entry(const void* d_bases, size_t n_bases, size_t base_offset, const
   return ZK_OK;
 }
 
+// A batch of exponent vectors over one base vector (msm_host.hpp: msm_device_batch).  The Source / density arithmetic belongs to the base vector
+// and the map, so it is done once; a vector's Source error is translated as msm_dev_entry translates it.  Exponents beyond the bases
+// (UnexpectedEof) are every vector's error unless the vector has an earlier one: the single call decides, vector by vector.
+template <int GROUP>
+int msm_batch_dev_entry(const void* d_bases, size_t n_bases, size_t base_offset, const void* d_scalars, size_t n_scalars, size_t scalar_stride,
+                        size_t n_vectors, const uint32_t* density, size_t density_bits, uint32_t flags, void* stream, uint64_t* out_xyz, int* rcs,
+                        long long* err_indices) {
+  t_last_err_index = -1;
+  constexpr size_t words = GROUP == 1 ? 12 : 24;
+  if (!out_xyz || !rcs || !err_indices || n_vectors == 0 || scalar_stride < n_scalars || (n_scalars && !d_scalars) || (n_bases && !d_bases)) return ZK_ERR_BAD_ARGS;
+  if (n_bases >= (1ull << 31) || n_scalars >= (1ull << 31) || scalar_stride >= (1ull << 31) || n_vectors >= (1ull << 31)) return ZK_ERR_BAD_ARGS;
+  if (flags & ~MI355ZK_MSM_SCALARS_MONTGOMERY) return ZK_ERR_BAD_ARGS;
+  const DensityPlan P = plan_density(n_bases, base_offset, n_scalars, density, density_bits);
+  if (P.eof_index >= 0 || n_vectors == 1) {
+    for (size_t v = 0; v < n_vectors; ++v) {
+      rcs[v] = msm_dev_entry<GROUP>(d_bases, n_bases, base_offset, (const char*)d_scalars + v * scalar_stride * 32, n_scalars, density, density_bits, stream,
+                                    out_xyz + v * words, 1, 0, flags);
+      err_indices[v] = t_last_err_index;
+    }
+    return ZK_OK;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const uint64_t n = P.live();
+  uint32_t* d_density = nullptr;
+  uint32_t* d_prefix = nullptr;
+  DeviceBufPool::Lease density_lease;
+  if (density != nullptr && n > 0) {
+    int dev = 0;
+    ZK_HIP(hipGetDevice(&dev));
+    const size_t dwords = (n + 31) / 32;
+    if (int rc = density_lease.acquire(dev, dwords * 8, st)) return rc;
+    d_density = (uint32_t*)density_lease.p();
+    d_prefix = d_density + dwords;
+    ZK_HIP(hipMemcpyAsync(d_density, density, dwords * 4, hipMemcpyHostToDevice, st));
+    ZK_HIP(hipMemcpyAsync(d_prefix, P.prefix.data(), dwords * 4, hipMemcpyHostToDevice, st));
+  }
+  const bool mont = (flags & MI355ZK_MSM_SCALARS_MONTGOMERY) != 0;
+  int rc;
+  if (GROUP == 1) rc = msm_g1_batch_device(d_bases, n_bases, base_offset, d_scalars, n, scalar_stride, (uint32_t)n_vectors, d_density, d_prefix, st, out_xyz, rcs, err_indices, mont);
+  else rc = msm_g2_batch_device(d_bases, n_bases, base_offset, d_scalars, n, scalar_stride, (uint32_t)n_vectors, d_density, d_prefix, st, out_xyz, rcs, err_indices, mont);
+  if (rc != ZK_OK) return rc;
+  for (size_t v = n_vectors; v-- > 0;) {
+    if (rcs[v] == ZK_ERR_UNEXPECTED_IDENTITY) err_indices[v] = (long long)P.select((uint64_t)(err_indices[v] - (long long)base_offset));   // (msm_dev_entry)
+    else if (rcs[v] != ZK_ERR_BAD_ARGS) err_indices[v] = -1;
+    if (rcs[v] != ZK_OK) t_last_err_index = err_indices[v];   // (the thread's last-error index: the first failing vector's)
+  }
+  return ZK_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Host-buffer entry points (SURVEY 8b "Ownership"): the caller's bases and scalars live in (pageable) host memory.
 //   * BASES CACHE (bases_cache.hpp): the device copy of a base vector the caller has PINNED stays on the device; vectors that were not
@@ -382,6 +431,8 @@ int msm_host_entry(const uint8_t* bases, size_t n_bases, size_t base_offset, con
   return msm_host_run<GROUP>(bases, n_bases, base_offset, scalars, n_scalars, density, density_bits, out_xyz, K, L);
 }
 
+template int msm_batch_dev_entry<1>(const void*, size_t, size_t, const void*, size_t, size_t, size_t, const uint32_t*, size_t, uint32_t, void*, uint64_t*, int*, long long*);
+template int msm_batch_dev_entry<2>(const void*, size_t, size_t, const void*, size_t, size_t, size_t, const uint32_t*, size_t, uint32_t, void*, uint64_t*, int*, long long*);
 template int msm_dev_entry<1>(const void*, size_t, size_t, const void*, size_t, const uint32_t*, size_t, void*, uint64_t*, uint32_t, uint32_t, uint32_t, MsmChunks*, bool);
 template int msm_dev_entry<2>(const void*, size_t, size_t, const void*, size_t, const uint32_t*, size_t, void*, uint64_t*, uint32_t, uint32_t, uint32_t, MsmChunks*, bool);
 template int msm_host_entry<1>(const uint8_t*, size_t, size_t, const uint64_t*, size_t, const uint32_t*, size_t, uint64_t*, const RecordLayout&);

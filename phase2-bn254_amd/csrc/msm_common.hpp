@@ -67,4 +67,19 @@ constexpr uint32_t MSM_TREE_SLICE = 512;
 constexpr uint32_t MSM_MAX_LEVELS = 8;
 constexpr uint32_t MSM_MAX_JOBS = MSM_MAX_LEVELS + 24;
 
+// a BATCH: n_vectors exponent vectors of n exponents over ONE base vector and ONE density map (msm_plan.hpp: MsmRequest::n_vectors, msm_batch_split)
+// What bounds the bucket sets WL = B * WD of one pipeline pass, from the uses of WL, ncell and n_buckets in the planner, the partition,
+// the accumulation and the reduction (none of them indexes MsmGeom::width / shift by a bucket set: those are per window of ONE vector):
+//   u32 products      n_buckets = WL * nb, m = n * WL and the index lists' vals_cap <= 0xfffffff0; the grids n_st * WL, lvl_chunks * WL and
+//                     first_block[n_jobs] * WL (the last one checked as such; the others are below m and n_buckets)
+//   choose_part       fits_lds: WL * nbin 16-bit counters within 2 * PART_LDS_A at the coarsest bins (nbin = ceil(nb / 4096)): 77824 / nbin sets
+//   gates, not limits small_scan (n_st * ncell <= 2^16), quad_max_chunks, MSM_PAIR_MAX_BUCKETS and the split launch only choose between kernels
+//                     that all take any WL; MSM_HEAVY_BLOCKS caps the buckets of the segment-parallel path, the others run a lane each
+//   back_bytes()      WL * n_out records come back through ONE pinned buffer, grow-only and one per concurrent caller (the prover has eight):
+//                     4096 sets x 30 records x 256 B (G2) = 30 MiB.  THIS is the binding one for short vectors -- at n <= 2^13 the u32 and
+//                     LDS limits allow 2^16 sets and more -- and it sets the constant; from ~2^18 exponents on the workspace itself binds first
+//                     (MSM_BATCH_WS_MAX: a 2^20-point G1 batch of 16 vectors is 256 sets and 5 GiB of keys, pairs and bucket records).
+constexpr uint32_t MSM_BATCH_MAX_WINDOWS = 4096;       // bucket sets per pipeline pass
+constexpr uint64_t MSM_BATCH_WS_MAX = (uint64_t)8 << 30;  // workspace bytes per pipeline pass
+
 }  // namespace zk

@@ -53,6 +53,19 @@ int segsum_g1_device(const void* d_points, uint64_t nnz, const uint32_t* d_row_p
   return segsum_device<Fq>((const G1Affine*)d_points, nnz, d_row_ptr, n_rows, st, (G1Affine*)d_out);
 }
 
+// a batch of exponent vectors over one base vector (msm_host.hpp: msm_device_batch): out_xyz = n_vectors x 12 words
+int msm_g1_batch_device(const void* d_bases, uint64_t n_bases, uint64_t base_offset, const void* d_scalars, uint64_t n, uint64_t scalar_stride,
+                        uint32_t n_vectors, const uint32_t* d_density, const uint32_t* d_dprefix, hipStream_t st, uint64_t* out_xyz, int* rcs,
+                        long long* err_indices, bool scalars_mont) {
+  std::vector<G1Jacobian> r(n_vectors);
+  int rc = msm_device_batch<Fq>((const G1Affine*)d_bases, n_bases, base_offset, (const uint32_t*)d_scalars, n, scalar_stride, n_vectors, d_density, d_dprefix, st,
+                                r.data(), rcs, err_indices, scalars_mont);
+  if (rc == ZK_OK)
+    for (uint32_t v = 0; v < n_vectors; ++v)
+      if (rcs[v] == ZK_OK) std::memcpy(out_xyz + (size_t)v * 12, &r[v], sizeof r[v]);
+  return rc;
+}
+
 void msm_release_g1() { ws_release_all(); }
 
 }  // namespace zk

@@ -443,6 +443,126 @@ int msm_device(const Affine<F>* d_bases, uint64_t n_bases, uint64_t base_offset,
   return msm_finish_set(A, lease, lk, d_bases, d_sc_first, out2, true, err_index_out);
 }
 
+// ---- A BATCH: n_vectors exponent vectors (vector v at d_scalars + v * scalar_stride * 8 words) over ONE base vector and ONE density map:
+// out[v] / rcs[v] / err_index[v] are what msm_device returns for vector v alone.  The vectors are an axis in FRONT of the pipeline:
+// the batched digit kernel writes vector v's WD key planes at v * WD, and the partition, the accumulation and the reduction run
+// unchanged over WL = B' * WD bucket sets (MsmRequest::n_vectors) -- one launch sequence and one copy back for B' vectors.  A batch
+// beyond the limits of one pass (msm_plan.hpp: msm_batch_split) runs several passes over consecutive vectors in the same workspace
+// lease; every pass ends with ONE copy back and one join per vector (msm_join_batch), the last pass's after the workspace is given up.
+// ERRORS: the pipeline's two error words stay call-wide.  A pass that sets either is discarded and its vectors are run by msm_device
+// one by one, after the batch's device work: their return codes, error indices and points come from there (caller bugs, not a
+// path to make fast).  The return value is that of the call as a whole (refused arguments, a device failure).
+template <class F>
+int msm_device_batch(const Affine<F>* d_bases, uint64_t n_bases, uint64_t base_offset, const uint32_t* d_scalars, uint64_t n, uint64_t scalar_stride,
+                     uint32_t n_vectors, const uint32_t* d_density, const uint32_t* d_dprefix, hipStream_t st, Jacobian<F>* out, int* rcs,
+                     long long* err_index_out, bool scalars_mont) {
+  if (n_vectors == 0 || scalar_stride < n) return ZK_ERR_BAD_ARGS;
+  for (uint32_t v = 0; v < n_vectors; ++v) out[v] = Jacobian<F>::zero(), rcs[v] = ZK_OK, err_index_out[v] = -1;
+  if (n == 0) return ZK_OK;
+  if (n_bases > 0x7fffffffull || n > 0x7fffffffull) return ZK_ERR_BAD_ARGS;
+  auto single = [&](uint32_t v) {
+    rcs[v] = msm_device<F>(d_bases, n_bases, base_offset, d_scalars + (uint64_t)v * scalar_stride * 8, n, d_density, d_dprefix, st, &out[v],
+                           &err_index_out[v], false, nullptr, nullptr, 1, 0, scalars_mont);
+  };
+  const MsmKnobs K = msm_knobs();
+  const int group = (int)(sizeof(F) / sizeof(Fq));
+  const uint32_t per = n_vectors == 1 ? 1u : msm_batch_split(n, n_vectors, choose_geom(n, group, 1, K), group, K);
+  if (per <= 1) {   // one vector, or a vector so long that two do not fit a pass: today's path
+    if (n_vectors > 1 && K.fused_a) return ZK_ERR_BAD_ARGS;   // (as launch_digits answers a batch under the fused pass A)
+    for (uint32_t v = 0; v < n_vectors; ++v) single(v);
+    return ZK_OK;
+  }
+  int dev = 0;
+  ZK_HIP(hipGetDevice(&dev));
+  // the plans: full passes of `per` vectors and, when per does not divide the batch, a shorter last one
+  MsmRequest R;
+  R.group = group;
+  R.n = n;
+  R.base_offset = base_offset;
+  R.n_vectors = per;
+  const MsmPlan P_full = msm_plan(R, K);
+  if (P_full.rc) return P_full.rc;
+  const uint32_t n_pass = msm_batch_passes(n_vectors, per), last_cnt = msm_batch_pass(n_vectors, per, n_pass - 1).count;
+  MsmPlan P_last;
+  if (last_cnt != per && last_cnt > 1) {
+    R.n_vectors = last_cnt;
+    P_last = msm_plan(R, K);
+    if (P_last.rc) return P_last.rc;
+  }
+  const bool last_single = last_cnt == 1;   // a lone last vector takes the single call
+  const uint32_t n_batched = last_single ? n_pass - 1 : n_pass;
+  auto plan_of = [&](uint32_t p) -> const MsmPlan& { return (p + 1 == n_pass && last_cnt != per) ? P_last : P_full; };
+  std::vector<uint8_t> redo(n_vectors, 0);
+  {
+    struct Inflight {
+      std::atomic<int>& c;
+      explicit Inflight(std::atomic<int>& x) : c(x) { c.fetch_add(1, std::memory_order_relaxed); }
+      ~Inflight() { c.fetch_sub(1, std::memory_order_relaxed); }
+    } inflight(g_msm_inflight[dev & 15]);
+    int rc = part_configure<F>(dev);
+    if (rc) return rc;
+    size_t ws_bytes = 0, pin_bytes = 0;
+    for (uint32_t p = 0; p < n_batched; ++p) {
+      ws_bytes = std::max(ws_bytes, plan_of(p).L.total_bytes);
+      pin_bytes = std::max(pin_bytes, plan_of(p).L.back_bytes());
+    }
+    PinLease pin;
+    if (int prc = pin_acquire(dev, pin_bytes, &pin)) return prc;
+    Workspace& dev_ws = ws_of(dev);
+    std::unique_lock<std::mutex> lk(dev_ws.mu, std::defer_lock);
+    void* base = nullptr;
+    SmallWsLease lease;
+    if (ws_bytes <= WS_SMALL) {
+      rc = tws_acquire(dev, ws_bytes, st, &lease, &base);
+    } else {
+      lk.lock();
+      rc = dev_ws.buf.reserve(ws_bytes);
+      base = dev_ws.buf.p;
+    }
+    if (rc) return rc;
+    double join_us = 0;
+    for (uint32_t p = 0; p < n_batched; ++p) {
+      const MsmPlan& P = plan_of(p);
+      const MsmBatchPass pass = msm_batch_pass(n_vectors, per, p);
+      const MsmCall<F> A{{P, K, group, dev, st, n, base_offset, 0, d_density, d_dprefix, scalars_mont, scalar_stride}, MsmWs<F>((char*)base, P.L), false};
+      const ChunkPlan& C = P.chunks[0];
+      lease.idle = false;
+      ZK_HIP(hipMemsetAsync(A.ws.d_err, 0xff, 16, st));
+      rc = launch_digits(A, A.ws, C, d_scalars + (uint64_t)pass.first * scalar_stride * 8);
+      if (rc == ZK_OK) rc = launch_partition(A, A.ws, C);
+      if (rc == ZK_OK) rc = launch_accumulate(A, C, d_bases, false);
+      if (rc) return rc;
+      prof_begin(msm_slots().red, st);
+      if (int rrc = launch_reduce(A)) return rrc;
+      prof_end(msm_slots().red, st);
+      if (msm_checkpoint(A, "reduce", C)) return (int)ZK_ERR_DEVICE;
+      // ONE copy back per pass: the window sums of all its vectors and the two error words
+      ZK_HIP(hipMemcpyAsync(pin.slot->p, A.ws.wsums, P.L.back_bytes(), hipMemcpyDeviceToHost, st));
+      ZK_HIP(hipStreamSynchronize(st));
+      lease.idle = true;
+      if (p + 1 == n_batched) {   // the device is done with the workspace: the last joins are host work beside the next call
+        if (lk.owns_lock()) lk.unlock();
+        lease.release();
+      }
+      unsigned long long h_errs[2];
+      std::memcpy(h_errs, (const char*)pin.slot->p + (P.L.back_bytes() - 16), 16);
+      if (h_errs[0] != ~0ull || h_errs[1] != ~0ull) {   // some vector of the pass has a Source error or a non-canonical exponent: the single calls say which
+        for (uint32_t v = 0; v < pass.count; ++v) redo[pass.first + v] = 1;
+        continue;
+      }
+      const auto t_join0 = std::chrono::steady_clock::now();
+      msm_join_batch<F>(P, reinterpret_cast<const XYZZ<F>*>(pin.slot->p), pass.count, K.join_serial, out + pass.first);
+      join_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_join0).count();
+    }
+    if (K.trace_join)
+      std::fprintf(stderr, "[mi355zk] msm batch n=%llu x %u: host joins of %u passes: %.1f us\n", (unsigned long long)n, n_vectors, n_batched, join_us);
+  }
+  if (last_single) redo[n_vectors - 1] = 1;
+  for (uint32_t v = 0; v < n_vectors; ++v)
+    if (redo[v]) single(v);
+  return ZK_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Segmented sum of affine points: out[r] = sum of points[row_ptr[r] .. row_ptr[r+1]), normalised to affine.
 // This is the bucket accumulation above with the rows of a CSR matrix as the "buckets" (size-ordered lanes,

@@ -67,15 +67,23 @@ inline Jacobian<F> window_sum(const JoinTerms& J, const XYZZ<F>* h_wsums, uint32
   return horner(by_exp);
 }
 
+// the helper threads of this unit's joins: the window sums of one call, or whole vectors of a batch (msm_join_batch)
+inline JoinPool& msm_join_pool() {
+  static JoinPool pool;
+  return pool;
+}
+
 // *result = sum_w 2^shift_w * T_w,  T_w = A_0 + L_0*(A_1 + L_1*(... + sum_j 2^j Bits_j)):  every partial sum
 // P[w][k] carries a power of two 2^(shift_w + e_k).  Terms are collected per exponent and ONE Horner pass
 // (a doubling per bit, multiexp.rs:146-154) joins everything -- ~270 doublings instead of W * (c + e_max).
-// h_wsums: P.WL * P.n_out records, window-major.  serial: never the helper threads (MsmKnobs::join_serial).
+// h_wsums: WL * P.n_out records, window-major.  serial: never the helper threads (MsmKnobs::join_serial).
 // ran_parallel (tests): whether the helper threads took the window sums.
+// WL: the bucket sets joined -- P.WL for a single call; P.WD for ONE vector of a batch, whose records are the slice
+// h_wsums + v * P.WD * P.n_out of what came back (the plan's WL counts every vector's sets).
 template <class F>
-void msm_join(const MsmPlan& P, const XYZZ<F>* h_wsums, bool serial, Jacobian<F>* result, bool* ran_parallel = nullptr) {
+void msm_join(const MsmPlan& P, uint32_t WL, const XYZZ<F>* h_wsums, bool serial, Jacobian<F>* result, bool* ran_parallel = nullptr) {
   const MsmGeom G = P.G;   // (a copy, like J: see JoinTerms)
-  const uint32_t WL = P.WL, w_lo = P.w_lo, w_hi = P.w_hi;
+  const uint32_t w_lo = P.w_lo, w_hi = P.w_hi;
   const bool tmode = P.tmode;
   JoinTerms J;
   J.n_out = P.n_out;
@@ -84,9 +92,8 @@ void msm_join(const MsmPlan& P, const XYZZ<F>* h_wsums, bool serial, Jacobian<F>
   // The window sums T_w are independent: with the helper threads free (JoinPool: a single caller -- the prover's eight
   // concurrent joins take the single-threaded paths below instead), every T_w is joined from its n_out terms in parallel and
   // only the chain over the windows stays serial: G2 at 2^20 0.48 -> 0.26 ms of host time, G1 0.13 -> 0.08 ms.
-  static JoinPool join_pool;
   std::vector<Jacobian<F>> T(WL);
-  const bool parallel = !serial && WL >= 4 && join_pool.run(WL, [&](uint32_t wl) { T[wl] = window_sum(J, h_wsums, wl); });
+  const bool parallel = !serial && WL >= 4 && msm_join_pool().run(WL, [&](uint32_t wl) { T[wl] = window_sum(J, h_wsums, wl); });
   if (ran_parallel) *ran_parallel = parallel;
   Jacobian<F> acc;
   if (parallel && G.rmul == 1) {
@@ -120,6 +127,22 @@ void msm_join(const MsmPlan& P, const XYZZ<F>* h_wsums, bool serial, Jacobian<F>
     }
   }
   *result = acc;
+}
+template <class F>
+void msm_join(const MsmPlan& P, const XYZZ<F>* h_wsums, bool serial, Jacobian<F>* result, bool* ran_parallel = nullptr) {
+  msm_join<F>(P, P.WL, h_wsums, serial, result, ran_parallel);
+}
+
+// The joins of a batch: vector v from its WD * n_out records.  The vectors are independent, so with the helper threads free each takes
+// whole vectors (a G2 join is ~0.27 ms of host time: sixteen in a row would eat what the batch saves); otherwise -- the prover's eight
+// concurrent calls -- one after the other on the caller.
+template <class F>
+void msm_join_batch(const MsmPlan& P, const XYZZ<F>* h_wsums, uint32_t n_vectors, bool serial, Jacobian<F>* results, bool* ran_parallel = nullptr) {
+  const size_t per = (size_t)P.WD * P.n_out;
+  auto one = [&](uint32_t v) { msm_join<F>(P, P.WD, h_wsums + v * per, true, &results[v]); };
+  const bool parallel = !serial && n_vectors >= 2 && msm_join_pool().run(n_vectors, one);
+  if (ran_parallel) *ran_parallel = parallel;
+  if (!parallel) for (uint32_t v = 0; v < n_vectors; ++v) one(v);
 }
 
 }  // namespace

@@ -213,6 +213,53 @@ __global__ void __launch_bounds__(256) msm_digits_plain_kernel(const uint32_t* _
   });
 }
 
+// The plain digit kernel over a BATCH of exponent vectors that share the base vector and the density map (MsmRequest::n_vectors): the
+// vector on blockIdx.y, exponent i of vector v at scalars + (v * scalar_stride + i) * 8, its G.W keys on the planes v * G.W + w -- the
+// partition and everything behind it then see n_vectors * G.W windows of ONE call.  Same block as the plain kernel: a wave reads 64
+// consecutive 32-byte exponents (2 KiB, two 16-byte loads per lane) and writes 256 consecutive bytes per key plane; the grid is
+// (ceil(kstride / 256), n_vectors), so a short vector still brings n_vectors times the workgroups of its single call.  The density word
+// of exponent i is one load per lane, the same word for every v.  The non-canonical-exponent word takes the lowest INDEX over all
+// vectors: the call only needs to know that some vector has one (msm_device_batch then runs that pass's vectors one by one).
+template <uint32_t RM>
+__global__ void __launch_bounds__(256) msm_digits_batch_kernel(const uint32_t* __restrict__ scalars, uint64_t n, uint64_t scalar_stride,
+                                                              const uint32_t* __restrict__ density, MsmGeom G, int scalars_mont, uint64_t kstride,
+                                                              uint32_t* __restrict__ keys, unsigned long long* __restrict__ err_scalar) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t WD = G.W;
+  uint32_t* __restrict__ kv = keys + (uint64_t)blockIdx.y * WD * kstride;   // plane 0 of this vector
+  if (i >= n) {
+    // the (at most three) slots between the key planes: "no bucket", as the plain kernel leaves them
+    if (i < kstride) for (uint32_t w = 0; w < WD; ++w) kv[(uint64_t)w * kstride + i] = G.nb;
+    return;
+  }
+  bool active = true;
+  if (density != nullptr) active = (density[i >> 5] >> (i & 31)) & 1;
+  uint32_t s[9];
+  const uint4* sp = reinterpret_cast<const uint4*>(scalars + ((uint64_t)blockIdx.y * scalar_stride + i) * 8);
+  const uint4 s0 = sp[0], s1 = sp[1];
+  s[0] = s0.x; s[1] = s0.y; s[2] = s0.z; s[3] = s0.w; s[4] = s1.x; s[5] = s1.y; s[6] = s1.z; s[7] = s1.w; s[8] = 0;
+  if (scalars_mont) {
+    Fr f;
+#pragma unroll
+    for (int l = 0; l < 8; ++l) f.l[l] = s[l];
+    f = to_canonical(f);
+#pragma unroll
+    for (int l = 0; l < 8; ++l) s[l] = f.l[l];
+  }
+  const uint32_t any = s[0] | s[1] | s[2] | s[3] | s[4] | s[5] | s[6] | s[7];
+  if (active && (s[7] >> 30)) {   // not a canonical FrRepr: see msm_digits_hist_kernel
+    atomicMin(err_scalar, (unsigned long long)i);
+    active = false;
+  }
+  if (!active || any == 0) {
+    for (uint32_t w = 0; w < WD; ++w) kv[(uint64_t)w * kstride + i] = G.nb;
+    return;
+  }
+  msm_scalar_digits<RM>(s, G, 0u, WD, [&](uint32_t w, uint32_t d, uint32_t neg) {
+    if (w < WD) kv[(uint64_t)w * kstride + i] = d ? ((d - 1) | neg) : G.nb;
+  });
+}
+
 // tile_hist[st][wl][bin] from the keys of (window wl, super-tile st): one workgroup each
 __global__ void __launch_bounds__(PART_THREADS) msm_tile_hist_kernel(const uint32_t* __restrict__ keys, uint64_t n, uint64_t kstride, uint32_t nb,
                                                                      uint32_t WL, PartGeom P, uint16_t* __restrict__ tile_hist) {
@@ -835,7 +882,13 @@ int launch_digits(const MsmPartCall& A, const MsmPartWs& W, const ChunkPlan& C, 
   if (!C.small_scan) ZK_HIP(hipMemsetAsync(W.size_hist, 0, MSM_SIZE_BINS * 4, st));   // (msm_scan_small_kernel clears it)
   if (C.np > BIG_SEG) ZK_HIP(hipMemsetAsync(W.gcnt, 0, P.L.big_col - P.L.gcnt, st));  // gcnt and gcur (big bins only: see the bucket pass)
   prof_begin(msm_slots().digits, st);
-  if (!A.knobs.fused_a) {
+  if (P.n_vectors > 1) {
+    // a batch (msm_device_batch): d_sc is vector 0; the tile histograms, like everything behind them, run over WL = n_vectors * WD planes
+    if (A.knobs.fused_a || P.tmode || A.scalar_stride < nc || P.n_vectors > 65535u) return (int)ZK_ERR_BAD_ARGS;
+    ZK_DISPATCH_RMUL(G.rmul, hipLaunchKernelGGL(msm_digits_batch_kernel<RM>, dim3((unsigned)((kstride + 255) / 256), P.n_vectors), dim3(256), 0, st, d_sc, nc,
+                                                A.scalar_stride, dens, G, A.scalars_mont ? 1 : 0, kstride, W.keys, W.d_err + 1));
+    hipLaunchKernelGGL(msm_tile_hist_kernel, dim3(PG.n_st * WL), dim3(PART_THREADS), (size_t)PG.nbin * 4, st, W.keys, C.np, kstride, G.nb, WL, PG, W.tile_hist);
+  } else if (!A.knobs.fused_a) {
     ZK_DISPATCH_RMUL(G.rmul, hipLaunchKernelGGL(msm_digits_plain_kernel<RM>, dim3((unsigned)((kstride + 255) / 256)), dim3(256), 0, st, d_sc, nc, dens, G,
                                                 P.w_lo, P.w_hi, A.scalars_mont ? 1 : 0, kstride, W.keys, W.d_err + 1, C.lo));
     hipLaunchKernelGGL(msm_tile_hist_kernel, dim3(PG.n_st * WL), dim3(PART_THREADS), (size_t)PG.nbin * 4, st, W.keys, C.np, P.tmode ? C.np : kstride, G.nb, WL, PG,
@@ -933,6 +986,15 @@ void msm_geometry(uint64_t n, uint32_t wgroups, uint32_t* c, uint32_t* W) {
   MsmGeom G = choose_geom(n, 1, wgroups ? wgroups : 1, msm_knobs());
   *c = G.c;
   *W = G.W;
+}
+
+// a batch of n_vectors vectors of n exponents (msm_device_batch): the windows of one vector and the vectors one pipeline pass takes
+void msm_batch_geometry(uint64_t n, uint32_t n_vectors, int group, uint32_t* max_windows, uint32_t* W, uint32_t* vectors_per_pass) {
+  *max_windows = MSM_BATCH_MAX_WINDOWS;
+  const MsmKnobs K = msm_knobs();
+  const MsmGeom G = choose_geom(n, group, 1, K);
+  *W = G.W;
+  *vectors_per_pass = msm_batch_split(n, n_vectors, G, group, K);
 }
 
 // table mode (msm_device): the window layout a table of n_bases points is built for -- width[w] bits per window, window w scaled by

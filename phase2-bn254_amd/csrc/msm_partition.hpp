@@ -45,6 +45,7 @@ struct MsmPartCall {
   uint64_t n, base_offset, table_stride;
   const uint32_t *d_density, *d_dprefix;  // cover the whole call
   bool scalars_mont;
+  uint64_t scalar_stride = 0;  // a batch (plan.n_vectors > 1): exponents between vector v and vector v + 1
 };
 
 struct MsmSlots { int digits, scan, scatter, bucket, sort, acc, heavy, red; };

@@ -270,6 +270,7 @@ struct MsmRequest {
   bool two_sets = false;            // a second base vector under the same exponents
   uint64_t table_stride = 0;        // != 0: table mode, windows of make_geom(table_c)
   uint32_t table_c = 0;
+  uint32_t n_vectors = 1;           // > 1: a BATCH -- that many exponent vectors of n exponents each over the one base vector (one pipeline pass)
 };
 
 // per chunk: its partition geometry, and what one lane may walk before its bucket counts as heavy
@@ -300,9 +301,10 @@ struct MsmPlan {
   int rc = ZK_OK;               // ZK_ERR_BAD_ARGS: the call is refused, nothing else is valid
   int group = 1;
   bool tmode = false;           // table mode: ONE bucket set serves all windows
+  uint32_t n_vectors = 1;       // a batch: WL = n_vectors * WD bucket sets, vector v owns sets [v * WD, (v + 1) * WD)
   MsmGeom G{};
   uint32_t WD = 0, w_lo = 0, w_hi = 0;  // this call's windows (digit planes)
-  uint32_t WL = 0;              // bucket sets: one per window, or ONE in table mode
+  uint32_t WL = 0;              // bucket sets: one per window (and per vector of a batch), or ONE in table mode
   uint32_t n_buckets = 0;
   uint64_t m_max = 0;
   // reduction: running-sum levels (msm_reduce_level_kernel, chunk length 2^lvl_logl) while more than final_max elements per window are
@@ -332,6 +334,9 @@ inline int msm_plan_fill(const MsmRequest& R, const MsmKnobs& K, MsmPlan& P) {
   if (R.wgroups == 0 || R.wgroup >= R.wgroups) return ZK_ERR_BAD_ARGS;
   const bool tmode = P.tmode = R.table_stride != 0;
   if (tmode && (R.wgroups != 1 || R.n_chunks != 1 || R.two_sets || R.table_c < 4 || R.table_c > 24 || R.base_offset > R.table_stride)) return ZK_ERR_BAD_ARGS;
+  const uint32_t B = P.n_vectors = R.n_vectors;
+  if (B == 0) return ZK_ERR_BAD_ARGS;
+  if (B > 1 && (tmode || R.n_chunks != 1 || R.cuts != nullptr || R.two_sets || R.wgroups != 1)) return ZK_ERR_BAD_ARGS;
   const uint64_t whole[2] = {0, n};
   const uint32_t n_chunks = R.n_chunks;
   const uint64_t* cuts = R.cuts ? R.cuts : whole;
@@ -348,10 +353,14 @@ inline int msm_plan_fill(const MsmRequest& R, const MsmKnobs& K, MsmPlan& P) {
   const uint32_t WD = P.WD = G.W / R.wgroups;
   P.w_lo = R.wgroup * WD;
   P.w_hi = P.w_lo + WD;
-  const uint32_t WL = P.WL = tmode ? 1u : WD;
+  // (a batch: the geometry above is that of ONE vector of n exponents; the vectors only multiply the bucket sets)
+  if (B > 1 && (uint64_t)B * WD > MSM_BATCH_MAX_WINDOWS) return ZK_ERR_BAD_ARGS;
+  const uint32_t WL = P.WL = tmode ? 1u : B * WD;
   if (tmode && (uint64_t)G.W * R.table_stride > 0x7fffffffull) return ZK_ERR_BAD_ARGS;  // (an index-list entry is a 31-bit base index + sign)
   const uint64_t m_max = P.m_max = tmode ? ((n_max + 3) & ~3ull) * WD : n_max * WL;
   if (m_max > 0xfffffff0ull) return ZK_ERR_BAD_ARGS;  // pair positions are u32
+  // bucket ids are u32 (a single call: W * nb <= 64 * 2^23), and a pair of lanes per bucket counts 2 * n_buckets threads in u32
+  if ((uint64_t)WL * G.nb > (B > 1 ? 0x7ffffff0ull : 0xfffffff0ull)) return ZK_ERR_BAD_ARGS;
   const uint32_t n_buckets = P.n_buckets = WL * G.nb;
   // chunk length per level: 2L serial additions per lane, so shorter chunks once lanes are scarce
   uint32_t final_cnt = G.nb, n_levels = 0;
@@ -401,6 +410,8 @@ inline int msm_plan_fill(const MsmRequest& R, const MsmKnobs& K, MsmPlan& P) {
     C.m = C.np * WL;
     C.P = choose_part(C.np, WL, G.nb, K);
     if (C.P.st == 0) return ZK_ERR_BAD_ARGS;
+    // a batch never leaves choose_part with a histogram its budget does not hold (one call's W <= 64 windows always fit at lo = PART_LO_MAX)
+    if (B > 1 && (uint64_t)WL * C.P.nbin * 2 > 2ull * PART_LDS_A) return ZK_ERR_BAD_ARGS;
     C.ncell = WL * C.P.nbin;
     C.small_scan = !K.no_small_scan && (uint64_t)C.P.n_st * C.ncell <= (1u << 16);
     // index lists: every bucket start is padded to a multiple of 4 entries (<= 3 per bucket), every bin region to 4
@@ -466,6 +477,9 @@ inline int msm_plan_fill(const MsmRequest& R, const MsmKnobs& K, MsmPlan& P) {
   for (uint32_t k = 0; k < P.n_out; ++k) P.e_max = std::max(P.e_max, P.e_k[k]);
   P.tree_cnt = n_levels ? P.lvl_chunks[0] : final_cnt;
   P.tree_tmp = (uint64_t)P.n_out * ((P.tree_cnt + MSM_TREE_SLICE - 1) / MSM_TREE_SLICE);
+  // the grid of a tree launch is (blocks per window) x WL: at most n_out + 2 jobs of at most max(slices of the longest job, rows, columns) blocks
+  if (B > 1 && (uint64_t)(P.n_out + 2) * std::max<uint64_t>((P.tree_cnt + MSM_TREE_SLICE - 1) / MSM_TREE_SLICE, std::max(t_rows, t_cols)) * WL > 0x7fffffffull)
+    return ZK_ERR_BAD_ARGS;
 
   MsmLayout& L = P.L;
   size_t off = 0;
@@ -495,6 +509,36 @@ inline MsmPlan msm_plan(const MsmRequest& R, const MsmKnobs& K) {
   MsmPlan P;
   P.rc = msm_plan_fill(R, K, P);
   return P;
+}
+
+// ---- a batch (MsmRequest::n_vectors): how it is cut into pipeline passes; the limits are msm_common.hpp's MSM_BATCH_*
+// vectors per pipeline pass of a batch of B vectors of n exponents (G = choose_geom(n, group, 1, K)): the most those limits and msm_plan_fill allow, at
+// most B; 1 = no pass is worth its name (the caller runs single calls).  A batch runs ceil(B / split) passes over consecutive vectors.
+inline uint32_t msm_batch_split(uint64_t n, uint32_t B, const MsmGeom& G, int group, const MsmKnobs& K) {
+  if (B <= 1 || n == 0 || G.W == 0) return B ? 1u : 0u;
+  uint32_t per = std::min<uint32_t>(B, MSM_BATCH_MAX_WINDOWS / G.W);
+  while (per > 1) {
+    MsmRequest R;
+    R.group = group;
+    R.n = n;
+    R.n_vectors = per;
+    const MsmPlan P = msm_plan(R, K);
+    if (P.rc == ZK_OK && P.L.total_bytes <= MSM_BATCH_WS_MAX) break;
+    // the workspace is (nearly) linear in the vectors: aim at the budget, and always move
+    uint64_t next = per - 1;
+    if (P.rc == ZK_OK) next = std::min<uint64_t>(next, (uint64_t)((double)per * (double)MSM_BATCH_WS_MAX / (double)P.L.total_bytes));
+    else next = std::min<uint64_t>(next, per - per / 8);
+    per = (uint32_t)std::max<uint64_t>(next, 1);
+  }
+  return per;
+}
+// pass p of the ceil(B / per) passes: `count` consecutive vectors from `first`; every vector is in exactly one pass
+struct MsmBatchPass { uint32_t first, count; };
+inline uint32_t msm_batch_passes(uint32_t B, uint32_t per) { return per ? (B + per - 1) / per : 0; }
+inline MsmBatchPass msm_batch_pass(uint32_t B, uint32_t per, uint32_t p) {
+  const uint64_t first = (uint64_t)p * per;
+  if (first >= B) return {B, 0};
+  return {(uint32_t)first, (uint32_t)std::min<uint64_t>(per, B - first)};
 }
 
 }  // namespace zk

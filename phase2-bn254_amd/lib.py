@@ -58,6 +58,9 @@ SIGNATURES = {
     "mi355zk_bn254_g2_msm_table_build_dev": (_i, [_vp, _sz, _vp, _sz, _vp]),
     "mi355zk_bn254_g1_msm_table_dev": (_i, [_vp, _sz, _sz, _vp, _sz, _vp, _sz, _u32, _vp, _vp]),
     "mi355zk_bn254_g2_msm_table_dev": (_i, [_vp, _sz, _sz, _vp, _sz, _vp, _sz, _u32, _vp, _vp]),
+    "mi355zk_bn254_g1_msm_batch_dev": (_i, [_vp, _sz, _sz, _vp, _sz, _sz, _sz, _vp, _sz, _u32, _vp, _vp, _vp, _vp]),
+    "mi355zk_bn254_g2_msm_batch_dev": (_i, [_vp, _sz, _sz, _vp, _sz, _sz, _sz, _vp, _sz, _u32, _vp, _vp, _vp, _vp]),
+    "mi355zk_msm_batch_geometry": (_i, [_sz, _sz, _i, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
     "mi355zk_bn254_g1_dense_multiexp": (_i, [_vp, _vp, _sz, _vp]),
     "mi355zk_bn254_g2_dense_multiexp": (_i, [_vp, _vp, _sz, _vp]),
     "mi355zk_bn254_g1_merge_pairs": (_i, [_vp, _vp, _vp, _sz, _vp, _vp]),

@@ -227,3 +227,108 @@ def create_proof(pool: Worker, params: Parameters, prover: ProvingAssignment, r:
     g_c = _add(g_c, h())
     g_c = _add(g_c, l())
     return _to_affine(g_a), _to_affine(g_b), _to_affine(g_c)
+
+
+def _same_density(d0: DensityTracker, d1: DensityTracker) -> bool:
+    if d0 is d1:
+        return True
+    (w0, n0), (w1, n1) = d0.words(), d1.words()
+    return n0 == n1 and d0.get_total_density() == d1.get_total_density() and np.array_equal(w0, w1)
+
+
+def create_proofs(pool: Worker, params: Parameters, provers, rs, ss, concurrent: bool = True):
+    """create_proof for B ProvingAssignments of ONE circuit over one Parameters -- the loop of bellman/tests/mimc.rs:260-341, or
+    phase2/src/bin/prove.rs run once per witness.  The base vectors h, l, a, b_g1, b_g2 and the three density maps belong to the circuit,
+    so each of the eight multiexps of prover.rs:250-298 is ONE multiexp_many over the B exponent vectors (one pipeline on the device
+    instead of B), submitted from the same eight threads and streams as create_proof's.  The H chain runs per proof
+    (EvaluationDomain.h_poly) and so does the single-point assembly of prover.rs:300-333, with the proof's own r and s.
+    provers: ProvingAssignments with equal sizes and equal densities (compared word by word; ValueError otherwise); rs, ss: one
+    canonical integer per proof.  Returns [(a, b, c)] -- the bytes create_proof returns for each."""
+    import torch
+
+    from .bellman import multiexp_many
+
+    provers = list(provers)
+    rs, ss = list(rs), list(ss)
+    n_proofs = len(provers)
+    if not (n_proofs == len(rs) == len(ss)):
+        raise ValueError("create_proofs: one r and one s per ProvingAssignment")
+    if n_proofs == 0:
+        return []
+    p0 = provers[0]
+    for p in provers[1:]:
+        if (p.a.shape, p.b.shape, p.c.shape, p.input_assignment.shape, p.aux_assignment.shape) != (
+                p0.a.shape, p0.b.shape, p0.c.shape, p0.input_assignment.shape, p0.aux_assignment.shape) or p.a.device != p0.a.device:
+            raise ValueError("create_proofs: the ProvingAssignments differ in size: not one circuit")
+        if not (_same_density(p.a_aux_density, p0.a_aux_density) and _same_density(p.b_input_density, p0.b_input_density)
+                and _same_density(p.b_aux_density, p0.b_aux_density)):
+            raise ValueError("create_proofs: the ProvingAssignments differ in their densities: not one circuit")
+    vk = params.get_vk(p0.input_assignment.shape[0])
+    device = p0.a.device
+    ex = _pool8() if concurrent else None
+
+    def submit(bases, density, exponents):
+        if ex is None:
+            with torch.cuda.device(device):
+                futs = multiexp_many(pool, bases, density, exponents, scalars_montgomery=True)
+            return lambda i: futs[i].wait()
+
+        def call():
+            with torch.cuda.device(device), torch.cuda.stream(_thread_stream(device)):
+                return multiexp_many(pool, bases, density, exponents, scalars_montgomery=True)
+
+        f = ex.submit(call)
+        return lambda i: f.result()[i].wait()
+
+    # ---- h (prover.rs:217-247), per proof; the truncated coefficient vectors stacked
+    with torch.cuda.device(device):
+        hs = []
+        for p in provers:
+            a = EvaluationDomain.from_coeffs(p.a)
+            b = EvaluationDomain.from_coeffs(p.b)
+            c = EvaluationDomain.from_coeffs(p.c)
+            EvaluationDomain.h_poly(a, b, c, pool)
+            del b, c
+            coeffs = a.into_coeffs()
+            hs.append(coeffs[:coeffs.shape[0] - 1])
+        coeffs = torch.stack(hs).contiguous()
+        del hs
+        inputs = torch.stack([p.input_assignment for p in provers]).contiguous()
+        aux = torch.stack([p.aux_assignment for p in provers]).contiguous()
+    torch.cuda.current_stream(device).synchronize()   # (the multiexp threads use their own streams: see create_proof)
+    h = submit(params.get_h(coeffs.shape[1]), FullDensity(), coeffs)
+    l = submit(params.get_l(aux.shape[1]), FullDensity(), aux)  # noqa: E741
+    a_inputs_source, a_aux_source = params.get_a(inputs.shape[1], p0.a_aux_density.get_total_density())
+    a_inputs = submit(a_inputs_source, FullDensity(), inputs)
+    a_aux = submit(a_aux_source, p0.a_aux_density, aux)
+    b_input_density_total = p0.b_input_density.get_total_density()
+    b_aux_density_total = p0.b_aux_density.get_total_density()
+    b_g1_inputs_source, b_g1_aux_source = params.get_b_g1(b_input_density_total, b_aux_density_total)
+    b_g1_inputs = submit(b_g1_inputs_source, p0.b_input_density, inputs)
+    b_g1_aux = submit(b_g1_aux_source, p0.b_aux_density, aux)
+    b_g2_inputs_source, b_g2_aux_source = params.get_b_g2(b_input_density_total, b_aux_density_total)
+    b_g2_inputs = submit(b_g2_inputs_source, p0.b_input_density, inputs)
+    b_g2_aux = submit(b_g2_aux_source, p0.b_aux_density, aux)
+
+    if _is_zero(vk["delta_g1"]) or _is_zero(vk["delta_g2"]):      # prover.rs:300-304
+        raise SynthesisError(SynthesisError.UNEXPECTED_IDENTITY)
+    proofs = []
+    for i, (r, s) in enumerate(zip(rs, ss)):                      # prover.rs:300-333, per proof
+        g_a = _add(_mul(vk["delta_g1"], r, device), _from_affine(vk["alpha_g1"]))
+        g_b = _add(_mul(vk["delta_g2"], s, device), _from_affine(vk["beta_g2"]))
+        g_c = _mul(vk["delta_g1"], r * s % _R_ORDER, device)
+        g_c = _add(g_c, _mul(vk["alpha_g1"], s, device))
+        g_c = _add(g_c, _mul(vk["beta_g1"], r, device))
+        a_answer = _add(a_inputs(i), a_aux(i))
+        g_a = _add(g_a, a_answer)
+        a_answer = _mul(a_answer, s, device)
+        g_c = _add(g_c, a_answer)
+        b1_answer = _add(b_g1_inputs(i), b_g1_aux(i))
+        b2_answer = _add(b_g2_inputs(i), b_g2_aux(i))
+        g_b = _add(g_b, b2_answer)
+        b1_answer = _mul(b1_answer, r, device)
+        g_c = _add(g_c, b1_answer)
+        g_c = _add(g_c, h(i))
+        g_c = _add(g_c, l(i))
+        proofs.append((_to_affine(g_a), _to_affine(g_b), _to_affine(g_c)))
+    return proofs
