@@ -364,6 +364,32 @@ int mi355zk_bn254_fr_sparse_matvec_dev(void *d_out, const uint32_t *d_row_ptr, c
  * (and for the argument errors of the evaluating call, before any device work). */
 int mi355zk_bn254_fr_sparse_matvec_check_dev(const uint32_t *d_row_ptr, const uint32_t *d_col, const uint32_t *d_coeff_id,
                                              size_t n_coeffs, size_t n_x, size_t n_rows, size_t nnz, void *stream);
+/* ---- a batch of witnesses over one circuit (csrc/r1cs.hip): the same matrix times n_vectors vectors in ONE launch, and the satisfaction
+ * check of the result.  No more than MI355ZK_R1CS_MAX_VECTORS vectors per call (the second grid dimension of both kernels). */
+#define MI355ZK_R1CS_MAX_VECTORS 65535
+/* sparse_matvec_dev for n_vectors vectors: vector v is the n_x elements at d_x + v * x_stride * 32 bytes, its result the n_rows elements
+ * at d_out + v * out_stride * 32 bytes (strides in elements, as scalar_stride in msm_batch_dev; what lies between two vectors is neither
+ * read nor written).  A term's col, coeff_id and coefficient are loaded once per tile of vectors; every step returns the canonical residue,
+ * so out[v] is byte for byte what the single call writes for x[v], and n_vectors == 1 is the single call.  Operand and index range as
+ * above.  Asynchronous on `stream`, no host synchronisation.
+ * 3 (before any device work) = what the single call refuses; n_vectors == 0 or > MI355ZK_R1CS_MAX_VECTORS; x_stride < n_x; out_stride <
+ * n_rows; an out range [d_out, d_out + ((n_vectors - 1) out_stride + n_rows) 32) that overlaps the x range.  n_rows == 0 succeeds and
+ * launches nothing. */
+int mi355zk_bn254_fr_sparse_matvec_batch_dev(void *d_out, size_t out_stride, const uint32_t *d_row_ptr, const uint32_t *d_col,
+                                             const uint32_t *d_coeff_id, const void *d_coeffs, size_t n_coeffs, const void *d_x, size_t n_x,
+                                             size_t x_stride, size_t n_vectors, size_t n_rows, size_t nnz, void *stream);
+/* Is the R1CS satisfied: a[i] * b[i] == c[i] for every row i < n_rows of every vector (SynthesisError::Unsatisfiable, bellman/src/cs.rs:162;
+ * the reference's Groth16 path has no such check and leaves a wrong witness to the pairing).  d_a, d_b, d_c are device arrays of Montgomery
+ * Fr, read only; vector v's rows start at base + v * vector_stride * 32 bytes (stride in elements, >= n_rows); the three may be slices of
+ * one array -- the layout of the product above: a = out, b = out + m, c = out + 2 m, vector_stride >= 3 m.  first_bad[v] (HOST, n_vectors
+ * entries) is the lowest failing row of vector v or -1, n_bad[v] (HOST, may be NULL) the number of failing rows.  Synchronises `stream`.
+ * Operand range: canonical Montgomery Fr, which is what the product writes; for other words the verdict is unspecified, nothing faults.
+ * 3 (before any device work) = a NULL array with n_rows > 0; a NULL first_bad; n_vectors == 0 or > MI355ZK_R1CS_MAX_VECTORS;
+ * vector_stride < n_rows; n_rows >= 2^32.  n_rows == 0 fills -1 / 0 without device work.
+ * mi355zk_selftest_r1cs_check: the same row predicate on three HOST arrays of n_rows x 4 u64 (one vector, no device). */
+int mi355zk_bn254_fr_r1cs_check_dev(const void *d_a, const void *d_b, const void *d_c, size_t n_rows, size_t vector_stride, size_t n_vectors,
+                                    long long *first_bad, uint32_t *n_bad, void *stream);
+int mi355zk_selftest_r1cs_check(const uint64_t *a, const uint64_t *b, const uint64_t *c, size_t n_rows, long long *first_bad, uint32_t *n_bad);
 /* EvaluationDomain::divide_by_z_on_coset (domain.rs:207-234): a[i] *= (g^m - 1)^-1 with m = 2^log_n and g = 7 the multiplicative
  * generator (z(tau) = tau^m - 1, domain.rs:207-212) -- the division step of the prover's H polynomial (prover.rs:217-241), so that
  * the whole ifft / coset_fft / mul / sub / divide / icoset_fft pipeline stays in HBM.  Asynchronous on `stream`. */

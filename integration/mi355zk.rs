@@ -109,6 +109,8 @@ extern "C" {
     pub fn mi355zk_bn254_fr_from_repr_dev(d_out: *mut c_void, d_in: *const c_void, n: usize, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_fr_sparse_matvec_dev(d_out: *mut c_void, d_row_ptr: *const u32, d_col: *const u32, d_coeff_id: *const u32, d_coeffs: *const c_void, n_coeffs: usize, d_x: *const c_void, n_x: usize, n_rows: usize, nnz: usize, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_fr_sparse_matvec_check_dev(d_row_ptr: *const u32, d_col: *const u32, d_coeff_id: *const u32, n_coeffs: usize, n_x: usize, n_rows: usize, nnz: usize, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_bn254_fr_sparse_matvec_batch_dev(d_out: *mut c_void, out_stride: usize, d_row_ptr: *const u32, d_col: *const u32, d_coeff_id: *const u32, d_coeffs: *const c_void, n_coeffs: usize, d_x: *const c_void, n_x: usize, x_stride: usize, n_vectors: usize, n_rows: usize, nnz: usize, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_bn254_fr_r1cs_check_dev(d_a: *const c_void, d_b: *const c_void, d_c: *const c_void, n_rows: usize, vector_stride: usize, n_vectors: usize, first_bad: *mut c_longlong, n_bad: *mut u32, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_fr_divide_by_z_on_coset_dev(d_a: *mut c_void, log_n: u32, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_fr_h_combine_dev(d_a: *mut c_void, d_b: *const c_void, d_c: *const c_void, n: usize, log_n: u32, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_fr_h_poly_dev(d_a: *mut c_void, d_b: *mut c_void, d_c: *mut c_void, log_n: u32, flags: u32, stream: *mut c_void) -> c_int;

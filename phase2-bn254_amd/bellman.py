@@ -30,6 +30,7 @@ class SynthesisError(Exception):
     POLYNOMIAL_DEGREE_TOO_LARGE = "PolynomialDegreeTooLarge"  # domain.rs:66-79
     UNCONSTRAINED_VARIABLE = "UnconstrainedVariable"    # phase2/src/parameters.rs:340-346 (MPCParameters::new)
     MALFORMED_VERIFYING_KEY = "MalformedVerifyingKey"   # groth16/verifier.rs:40-42 (verify_proof)
+    UNSATISFIABLE = "Unsatisfiable"                     # cs.rs:162 (circom.UnsatisfiedConstraint: the witness check on the device)
 
     def __init__(self, kind: str, index: int = -1):
         super().__init__(kind if index < 0 else f"{kind} at exponent {index}")

@@ -377,6 +377,20 @@ def compile_circuit(circuit: CircomCircuit, device) -> CompiledCircuit:
     return cc
 
 
+def _witness_limbs(n_vars: int, witness, who: str) -> np.ndarray:
+    """One witness as prepare_prover_dev takes it -> (n_vars, 4) u64 canonical limbs; the refusals name `who`.  No device work."""
+    if isinstance(witness, (list, tuple)):
+        if len(witness) != n_vars:
+            raise ValueError(f"{who} does not have one value per variable")
+        return _limbs_array(v % _R_ORDER for v in witness) if n_vars else np.zeros((0, 4), dtype=np.uint64)
+    w = np.ascontiguousarray(witness, dtype=np.uint64)
+    if w.shape != (n_vars, 4):
+        raise ValueError(f"{who} does not have one value of 4 x u64 per variable")
+    if not _all_below_r(w):
+        raise ValueError(f"{who} holds a value >= r: canonical values required")
+    return w
+
+
 def prepare_prover_dev(compiled: CompiledCircuit, witness):
     """prepare_prover on a compiled circuit.  witness: the list of ints witness_from_json returns, or an (n_vars, 4) u64 array of
     canonical values (a value >= r is a ValueError), inputs first.  One upload, the conversion to Montgomery form, ONE sparse product into a
@@ -391,18 +405,9 @@ def prepare_prover_dev(compiled: CompiledCircuit, witness):
     from .bellman import DeviceError, _stream_ptr
 
     n_vars = compiled.num_inputs + compiled.num_aux
-    if isinstance(witness, (list, tuple)):
-        if len(witness) != n_vars:
-            raise ValueError("the witness does not have one value per variable")
-        w = _limbs_array(v % _R_ORDER for v in witness) if n_vars else np.zeros((0, 4), dtype=np.uint64)
-    else:
-        w = np.ascontiguousarray(witness, dtype=np.uint64)
-        if w.shape != (n_vars, 4):
-            raise ValueError("the witness does not have one value of 4 x u64 per variable")
-        if not _all_below_r(w):
-            raise ValueError("the witness holds a value >= r: canonical values required")
-        if not w.flags.writeable:
-            w = w.copy()                                  # (torch.from_numpy wants a writable array; nothing is written)
+    w = _witness_limbs(n_vars, witness, "the witness")
+    if not w.flags.writeable:
+        w = w.copy()                                      # (torch.from_numpy wants a writable array; nothing is written)
     lib = _lib.load()
     m = compiled.m
     with torch.cuda.device(compiled.device):
@@ -418,6 +423,139 @@ def prepare_prover_dev(compiled: CompiledCircuit, witness):
                                      compiled.a_aux_density, compiled.b_input_density, compiled.b_aux_density)
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# a BATCH of witnesses of one circuit: one upload, one conversion, one product (mi355zk_bn254_fr_sparse_matvec_batch_dev: the matrix is
+# the circuit's, as the base vectors are), and the check bellman's test constraint system has and its Groth16 path lacks -- is every
+# constraint satisfied, and if not, which one (mi355zk_bn254_fr_r1cs_check_dev), before any multiexp is queued
+_BATCH_PRODUCT = True   # profiles/r1cs_batch.md: the batch launch against the loop of single products
+
+
+class UnsatisfiedConstraint(SynthesisError):
+    """SynthesisError::Unsatisfiable (cs.rs:162) with what the device check found: `witness` (position in the batch), `index` (the
+    lowest failing row of the matrix = circuit.constraints[index]), `count` (failing rows of that witness) and the row's three values
+    a, b, c (canonical ints, a * b != c mod r)."""
+
+    def __init__(self, witness: int, index: int, count: int, a: int, b: int, c: int):
+        Exception.__init__(self, f"{SynthesisError.UNSATISFIABLE}: witness {witness} breaks constraint {index} (a * b != c); "
+                                 f"{count} of its constraints fail")
+        self.kind, self.index = SynthesisError.UNSATISFIABLE, index
+        self.witness, self.count, self.a, self.b, self.c = witness, count, a, b, c
+
+
+def prepare_provers_dev(compiled: CompiledCircuit, witnesses, check: bool = False):
+    """prepare_prover_dev for B witnesses of one compiled circuit.  witnesses: a list of what prepare_prover_dev takes, or ONE
+    (B, n_vars, 4) u64 array of canonical values; the refusals of prepare_prover_dev, before any device work, naming the witness.  ONE
+    upload, ONE conversion over B * n_vars elements, ONE product into a fresh (B, 3 m, 4) tensor; assignment v's a, b, c and its
+    input / aux assignments are views of these two tensors, the densities are the compiled circuit's, the bytes those of
+    prepare_prover_dev per witness.  check=True: one first_unsatisfied over the batch; raises UnsatisfiedConstraint for the lowest
+    failing witness at its first failing constraint.  Returns [ProvingAssignment]."""
+    import ctypes as C
+
+    import torch
+
+    from . import lib as _lib
+    from . import prover as _prover
+    from .bellman import DeviceError, _stream_ptr
+
+    n_vars = compiled.num_inputs + compiled.num_aux
+    if isinstance(witnesses, np.ndarray):
+        w = np.ascontiguousarray(witnesses, dtype=np.uint64)
+        if w.ndim != 3 or w.shape[1:] != (n_vars, 4):
+            raise ValueError("the witnesses are not a (B, n_vars, 4) array: one value of 4 x u64 per variable")
+        for k in range(w.shape[0]):
+            if not _all_below_r(w[k]):
+                raise ValueError(f"witness {k} holds a value >= r: canonical values required")
+    else:
+        rows = [_witness_limbs(n_vars, wk, f"witness {k}") for k, wk in enumerate(witnesses)]
+        w = np.stack(rows) if rows else np.zeros((0, n_vars, 4), dtype=np.uint64)
+    n_batch = w.shape[0]
+    if n_batch > _lib.R1CS_MAX_VECTORS:
+        raise ValueError(f"more than {_lib.R1CS_MAX_VECTORS} witnesses in one batch")
+    if n_batch == 0:
+        return []
+    if not w.flags.writeable:
+        w = w.copy()                                      # (torch.from_numpy wants a writable array; nothing is written)
+    lib = _lib.load()
+    m = compiled.m
+    matrix = (_cptr(compiled.row_ptr), _cptr(compiled.col), _cptr(compiled.coeff_id), _cptr(compiled.coeffs), compiled.n_coeffs)
+    with torch.cuda.device(compiled.device):
+        d_w = torch.from_numpy(w.view(np.int64)).to(compiled.device)
+        out = torch.empty((n_batch, 3 * m, 4), dtype=torch.int64, device=compiled.device)
+        rc = lib.mi355zk_bn254_fr_from_repr_dev(_cptr(d_w), _cptr(d_w), n_batch * n_vars, _stream_ptr())
+        if rc == 0 and _BATCH_PRODUCT:
+            rc = lib.mi355zk_bn254_fr_sparse_matvec_batch_dev(C.c_void_p(out.data_ptr()), 3 * m, *matrix, _cptr(d_w), n_vars, n_vars, n_batch,
+                                                              3 * m, compiled.nnz, _stream_ptr())
+        for v in range(0 if _BATCH_PRODUCT else n_batch):
+            if rc == 0:
+                rc = lib.mi355zk_bn254_fr_sparse_matvec_dev(C.c_void_p(out[v].data_ptr()), *matrix, _cptr(d_w[v]), n_vars, 3 * m, compiled.nnz, _stream_ptr())
+    if rc != 0:
+        raise DeviceError(f"mi355zk fr_sparse_matvec_batch failed rc={rc}")
+    provers = [_prover.ProvingAssignment(out[v, :m], out[v, m:2 * m], out[v, 2 * m:], d_w[v, :compiled.num_inputs], d_w[v, compiled.num_inputs:],
+                                         compiled.a_aux_density, compiled.b_input_density, compiled.b_aux_density) for v in range(n_batch)]
+    if check:
+        _raise_if_unsatisfied(provers)
+    return provers
+
+
+def _r1cs_check(tensors, n_rows: int, stride: int, n_vectors: int):
+    """one mi355zk_bn254_fr_r1cs_check_dev over n_vectors vectors that start at the three tensors and lie `stride` elements apart"""
+    import ctypes as C
+
+    import torch
+
+    from . import lib as _lib
+    from .bellman import DeviceError, _stream_ptr
+
+    first = (C.c_longlong * n_vectors)()
+    count = (C.c_uint32 * n_vectors)()
+    with torch.cuda.device(tensors[0].device):
+        rc = _lib.load().mi355zk_bn254_fr_r1cs_check_dev(_cptr(tensors[0]), _cptr(tensors[1]), _cptr(tensors[2]), n_rows, stride, n_vectors,
+                                                         first, count, _stream_ptr())
+    if rc != 0:
+        raise DeviceError(f"mi355zk fr_r1cs_check failed rc={rc}")
+    return [(None if first[v] < 0 else int(first[v]), int(count[v])) for v in range(n_vectors)]
+
+
+def first_unsatisfied(assignments):
+    """Is a[i] * b[i] == c[i] in every row: [(index of the lowest failing row or None, number of failing rows)], one pair per
+    ProvingAssignment (one assignment or a list of them, of any origin: prepare_prover, prepare_prover_dev, prepare_provers_dev).
+    ONE device call when the assignments are equally spaced slices of one allocation (what prepare_provers_dev returns), one call
+    each otherwise.  The call waits for the device."""
+    from . import prover as _prover
+
+    provers = [assignments] if isinstance(assignments, _prover.ProvingAssignment) else list(assignments)
+    if not provers:
+        return []
+    abc = []
+    for p in provers:
+        t = [x if x.is_contiguous() else x.contiguous() for x in (p.a, p.b, p.c)]
+        if not all(x.is_cuda and x.dim() == 2 and x.shape == t[0].shape and x.shape[1] == 4 and x.element_size() == 8 for x in t):
+            raise ValueError("first_unsatisfied: a, b and c are not three (n, 4) 64-bit device tensors of one length")
+        abc.append(t)
+    n_rows = abc[0][0].shape[0]
+    stride_bytes = abc[1][0].data_ptr() - abc[0][0].data_ptr() if len(abc) > 1 else 32 * n_rows
+    one_call = stride_bytes >= 32 * n_rows and stride_bytes % 32 == 0 and all(
+        t[k].shape[0] == n_rows and t[k].device == abc[0][0].device
+        and t[k].untyped_storage().data_ptr() == abc[0][k].untyped_storage().data_ptr()
+        and t[k].data_ptr() - abc[0][k].data_ptr() == v * stride_bytes for v, t in enumerate(abc) for k in range(3))
+    if one_call:
+        return _r1cs_check(abc[0], n_rows, stride_bytes // 32, len(abc))
+    return [_r1cs_check(t, t[0].shape[0], t[0].shape[0], 1)[0] for t in abc]
+
+
+def _raise_if_unsatisfied(provers):
+    """UnsatisfiedConstraint for the lowest witness of `provers` with a failing row, the row's three values copied back (96 bytes)"""
+    import torch
+
+    for v, (index, count) in enumerate(first_unsatisfied(provers)):
+        if index is not None:
+            p = provers[v]
+            row = torch.stack([p.a[index], p.b[index], p.c[index]]).cpu().numpy().view(np.uint64).reshape(3, 4)
+            r_inv = pow(_MONT_R, -1, _R_ORDER)
+            a, b, c = (int.from_bytes(row[k].tobytes(), "little") * r_inv % _R_ORDER for k in range(3))
+            raise UnsatisfiedConstraint(v, index, count, a, b, c)
+
+
 def filter_params(params):
     """filter_params (circom_circuit.rs:271-277): vk.ic, h, a, b_g1 and b_g2 without their points at infinity (the A / B queries
     are what the density maps index; l is left as it is, as in the reference)."""
@@ -426,10 +564,11 @@ def filter_params(params):
     return dict(params, vk=vk, h=keep(params["h"]), a=keep(params["a"]), b_g1=keep(params["b_g1"]), b_g2=keep(params["b_g2"]))
 
 
-def prove(pool, circuit: CircomCircuit, params, r: int, s: int, compiled: CompiledCircuit = None):
+def prove(pool, circuit: CircomCircuit, params, r: int, s: int, compiled: CompiledCircuit = None, check: bool = False):
     """prove (circom_circuit.rs:187-191) with the blinding scalars given (create_random_proof draws them from the RNG):
     returns the proof (a, b, c) as raw affine records.  params: the "params" dict of mpc_parameters_new / read_mpc_parameters.
-    compiled: compile_circuit(circuit, device) -- the witness is then evaluated on the device (prepare_prover_dev); same proof."""
+    compiled: compile_circuit(circuit, device) -- the witness is then evaluated on the device (prepare_prover_dev); same proof.
+    check: first_unsatisfied on the assignment; an unsatisfied witness raises UnsatisfiedConstraint before any multiexp is queued."""
     from . import prover as _prover
 
     p = filter_params(params)
@@ -443,13 +582,17 @@ def prove(pool, circuit: CircomCircuit, params, r: int, s: int, compiled: Compil
         if (compiled.num_inputs, compiled.num_aux, compiled.n) != (circuit.num_inputs, circuit.num_aux, len(circuit.constraints) + circuit.num_inputs):
             raise ValueError("`compiled` was not compiled from this circuit (variable or constraint counts differ)")
         assignment = prepare_prover_dev(compiled, circuit.witness)
+    if check:
+        _raise_if_unsatisfied([assignment])
     return _prover.create_proof(pool, _prover.Parameters(vk, p["h"], p["l"], p["a"], p["b_g1"], p["b_g2"]), assignment, r, s)
 
 
-def prove_many(pool, circuit: CircomCircuit, params, witnesses, rs, ss, compiled: CompiledCircuit = None):
-    """prove for many witnesses of one circuit: prepare_prover_dev per witness over ONE CompiledCircuit (compiled here when the caller
-    brings none), then prover.create_proofs -- every multiexp of the batch in one pipeline.  witnesses: what prepare_prover_dev takes,
-    one per proof; rs, ss: the blinding scalars, one pair per proof.  Returns [(a, b, c)]: what prove returns for each witness."""
+def prove_many(pool, circuit: CircomCircuit, params, witnesses, rs, ss, compiled: CompiledCircuit = None, check: bool = False):
+    """prove for many witnesses of one circuit: prepare_provers_dev over ONE CompiledCircuit (compiled here when the caller brings
+    none) -- one upload, one conversion, one product for the batch -- then prover.create_proofs -- every multiexp of the batch in one
+    pipeline.  witnesses: what prepare_provers_dev takes, one per proof; rs, ss: the blinding scalars, one pair per proof.  check: the
+    first unsatisfied witness raises UnsatisfiedConstraint before any multiexp is queued.  Returns [(a, b, c)]: what prove returns for
+    each witness."""
     from . import prover as _prover
 
     p = filter_params(params)
@@ -459,5 +602,5 @@ def prove_many(pool, circuit: CircomCircuit, params, witnesses, rs, ss, compiled
         compiled = compile_circuit(circuit, p["h"].device)
     if (compiled.num_inputs, compiled.num_aux, compiled.n) != (circuit.num_inputs, circuit.num_aux, len(circuit.constraints) + circuit.num_inputs):
         raise ValueError("`compiled` was not compiled from this circuit (variable or constraint counts differ)")
-    assignments = [prepare_prover_dev(compiled, w) for w in witnesses]
+    assignments = prepare_provers_dev(compiled, witnesses, check=check)
     return _prover.create_proofs(pool, _prover.Parameters(vk, p["h"], p["l"], p["a"], p["b_g1"], p["b_g2"]), assignments, rs, ss)

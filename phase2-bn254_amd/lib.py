@@ -22,7 +22,9 @@ H_INTO_REPR = 1   # MI355ZK_H_INTO_REPR: flags of fr_h_poly[_dev]
 FIXED_SCALARS_MONTGOMERY = 1   # MI355ZK_FIXED_SCALARS_MONTGOMERY: flags of fixed_base_mul_dev
 FIXED_BASES_LANE_TARGET = 262144  # MI355ZK_FIXED_BASES_LANE_TARGET: the lane count mi355zk_fixed_bases_plan aims for
 SHIFTED_DIFFERENCE_K = 16   # MI355ZK_SHIFTED_DIFFERENCE_K: outputs per shared inversion of g1_shifted_difference
-POINTS_PIECE = 1 << 18   # the piece of points_load / points_store (and of the accumulator entry points) when the caller passes 0
+R1CS_MAX_VECTORS = 65535   # MI355ZK_R1CS_MAX_VECTORS: vectors per call of fr_sparse_matvec_batch_dev / fr_r1cs_check_dev
+R1CS_BATCH_V = 1   # R1CS_BATCH_V of csrc/r1cs.hip: the vectors one workgroup of the batch product carries (its tile; the tests' edge sizes)
+POINTS_PIECE = 1 << 18  # the piece of points_load / points_store (and of the accumulator entry points) when the caller passes 0
 EXP_SAME_SCALAR, FFT_INVERSE, G2_TRUSTED_SUBGROUP = 1, 1, 2   # mode / flag bits of batch_exp, point_fft, sparse_matvec (include/mi355zk.h)
 
 _vp, _sz, _i, _u32 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32
@@ -96,6 +98,9 @@ SIGNATURES = {
     "mi355zk_bn254_fr_from_repr_dev": (_i, [_vp, _vp, _sz, _vp]),
     "mi355zk_bn254_fr_sparse_matvec_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _sz, _sz, _vp]),
     "mi355zk_bn254_fr_sparse_matvec_check_dev": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp]),
+    "mi355zk_bn254_fr_sparse_matvec_batch_dev": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _sz, _sz, _sz, _sz, _vp]),
+    "mi355zk_bn254_fr_r1cs_check_dev": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp]),
+    "mi355zk_selftest_r1cs_check": (_i, [_vp, _vp, _vp, _sz, _vp, _vp]),
     "mi355zk_bn254_fr_divide_by_z_on_coset_dev": (_i, [_vp, _u32, _vp]),
     "mi355zk_bn254_fr_h_combine_dev": (_i, [_vp, _vp, _vp, _sz, _u32, _vp]),
     "mi355zk_bn254_fr_h_poly_dev": (_i, [_vp, _vp, _vp, _u32, _u32, _vp]),
