@@ -423,6 +423,31 @@ int mi355zk_bn254_fr_domain_z(uint32_t log_n, const uint64_t tau[4], uint64_t ou
  * its index (at most 28 products) and walks its run with one product per element.  Operand range as for mul_assign above.  Asynchronous
  * on `stream`.  n == 0 succeeds and launches nothing.  3 = a NULL pointer with n > 0, n >= 2^32. */
 int mi355zk_bn254_fr_powers_dev(void *d_out, const uint64_t base[4], const uint64_t coeff[4], size_t n, void *stream);
+/* ---- a polynomial against points (csrc/fr_poly.hip): evaluation at z and division by (x - z) on device-resident coefficients, the two Fr
+ * steps of a KZG opening -- kate_divison (bellman/src/sonic/util.rs:444-463: q[n-2] = a[n-1], q[i-1] = a[i] + z q[i], serial there) and
+ * evaluate_at_consequitive_powers (sonic/util.rs:151-200, with first_power = 1).  coeffs: n x 32 B on the device, lowest degree first; z: n_points
+ * x 4 u64 on the HOST, read before the call returns; everything Montgomery Fr.  The recurrence is a suffix scan and runs as three launches (run and
+ * tile aggregates, tile carries, apply; evaluation is the first two) for all the points at once, the point being the second grid dimension, hence
+ * MI355ZK_POLY_MAX_POINTS.  Every step returns the canonical residue, so the results are the serial recurrence's byte for byte.
+ * Operand range: as for mul_assign / sub_assign above -- canonical Montgomery Fr, unchecked; a coefficient >= r makes the quotient elements below
+ * it and the remainder UNDEFINED, a point >= r everything of that point; the call still returns 0 and nothing faults.
+ * Both calls are asynchronous on `stream` (no host synchronisation); their scratch is the library's, per (device, stream).
+ * eval:   out[j] = sum_i coeffs[i] z_j^i; n == 0 gives 0.
+ * divide: coeffs(x) = q_j(x) (x - z_j) + rem_j, q_j = the n - 1 elements at d_q + j * q_stride * 32 B (stride in elements; what lies between two
+ *         quotients is neither read nor written), rem_j = coeffs(z_j) at d_rem + j * 32 B unless d_rem is NULL.  n == 1 writes no quotient and
+ *         rem = coeffs[0]; n == 0 writes no quotient and rem = 0.  d_q may not overlap d_coeffs.
+ * 3 (before any device work) = a NULL pointer with a non-zero count (d_rem apart); n >= 2^32; n_points == 0 or > MI355ZK_POLY_MAX_POINTS;
+ * q_stride < n - 1; a quotient range [d_q, d_q + ((n_points - 1) q_stride + n - 1) 32) that overlaps the coefficients. */
+#define MI355ZK_POLY_MAX_POINTS 65535
+int mi355zk_bn254_fr_poly_eval_dev(void *d_out, const void *d_coeffs, size_t n, const uint64_t *z, size_t n_points, void *stream);
+int mi355zk_bn254_fr_poly_divide_dev(void *d_q, size_t q_stride, void *d_rem, const void *d_coeffs, size_t n, const uint64_t *z, size_t n_points,
+                                     void *stream);
+/* The same routines compiled for the host, in the kernels' grouping into runs, tiles and carry chunks: one point, no device.  q: n - 1 elements
+ * (may be NULL for n <= 1), rem = coeffs(z).  3 = a NULL pointer with a non-zero count, n >= 2^32. */
+int mi355zk_selftest_fr_poly_divide(uint64_t *q, uint64_t rem[4], const uint64_t *coeffs, size_t n, const uint64_t z[4]);
+/* The compile-time geometry: coefficients per lane, coefficients per workgroup (tile), tiles per chunk of the carry kernel -- the sizes at
+ * which the code takes another path, for tests. */
+int mi355zk_fr_poly_geometry(uint32_t *run, uint32_t *tile, uint32_t *carry_width);
 /* Measured Montgomery-product rate of this library (the integer-ALU roofline the kernels are priced
  * against): `blocks` x 256 lanes each run 4 independent chains of `iters` products.  which: 0 Fq, 1 Fr.
  * out[0..3] = a*b^iters (Montgomery arithmetic, lane 0, chain 0) for a parity check; *ms = kernel time. */

@@ -117,6 +117,9 @@ extern "C" {
     pub fn mi355zk_bn254_fr_h_poly(h: *mut u64, a: *const u64, b: *const u64, c: *const u64, len: usize, log_n: u32, flags: u32) -> c_int;
     pub fn mi355zk_bn254_fr_domain_z(log_n: u32, tau: *const u64 /* [4] */, out: *mut u64 /* [4] */) -> c_int;
     pub fn mi355zk_bn254_fr_powers_dev(d_out: *mut c_void, base: *const u64 /* [4] */, coeff: *const u64 /* [4] */, n: usize, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_bn254_fr_poly_eval_dev(d_out: *mut c_void, d_coeffs: *const c_void, n: usize, z: *const u64, n_points: usize, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_bn254_fr_poly_divide_dev(d_q: *mut c_void, q_stride: usize, d_rem: *mut c_void, d_coeffs: *const c_void, n: usize, z: *const u64, n_points: usize, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_fr_poly_geometry(run: *mut u32, tile: *mut u32, carry_width: *mut u32) -> c_int;
     pub fn mi355zk_bn254_g1_sparse_matvec_dev(d_out_affine: *mut c_void, d_bases_affine: *const c_void, n_bases: usize, d_row_ptr: *const u32, d_col: *const u32, d_coeffs: *const c_void, n_rows: usize, nnz: usize, stream: *mut c_void, flags: c_int) -> c_int;
     pub fn mi355zk_bn254_g2_sparse_matvec_dev(d_out_affine: *mut c_void, d_bases_affine: *const c_void, n_bases: usize, d_row_ptr: *const u32, d_col: *const u32, d_coeffs: *const c_void, n_rows: usize, nnz: usize, stream: *mut c_void, flags: c_int) -> c_int;
     pub fn mi355zk_bn254_g1_sparse_matvec(out_affine: *mut u8, bases_affine: *const u8, n_bases: usize, row_ptr: *const u32, col: *const u32, coeffs: *const u64, n_rows: usize, nnz: usize, flags: c_int) -> c_int;

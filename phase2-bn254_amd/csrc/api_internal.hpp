@@ -115,6 +115,8 @@ int records_pack_run(int group, const void* d_raw, size_t n, const RecordLayout&
 int fr_h_combine(Fr* d_a, const Fr* d_b, const Fr* d_c, size_t n, const Fr& zinv, hipStream_t st);   // a[i] = (a[i] * b[i] - c[i]) * zinv, one pass
 int fr_into_repr(Fr* d_out, const Fr* d_in, size_t n, hipStream_t st);                                // Montgomery -> canonical (d_out may alias d_in)
 int fr_powers(Fr* d_out, const Fr& base, const Fr& coeff, size_t n, hipStream_t st);               // out[i] = coeff * base^i (Montgomery)
+// fr_poly.hip
+void fr_poly_release_all();   // the per-(device, stream) scratch of the polynomial division / evaluation (mi355zk_shutdown)
 
 // fr_random.hip: scalars first .. first + n - 1 of the stream (key, stream_id) of chacha.hpp as canonical FrRepr at d_out (16-byte aligned), enqueued on `st`
 struct FrRandomStream {

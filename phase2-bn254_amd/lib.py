@@ -23,6 +23,7 @@ FIXED_SCALARS_MONTGOMERY = 1   # MI355ZK_FIXED_SCALARS_MONTGOMERY: flags of fixe
 FIXED_BASES_LANE_TARGET = 262144  # MI355ZK_FIXED_BASES_LANE_TARGET: the lane count mi355zk_fixed_bases_plan aims for
 SHIFTED_DIFFERENCE_K = 16   # MI355ZK_SHIFTED_DIFFERENCE_K: outputs per shared inversion of g1_shifted_difference
 R1CS_MAX_VECTORS = 65535   # MI355ZK_R1CS_MAX_VECTORS: vectors per call of fr_sparse_matvec_batch_dev / fr_r1cs_check_dev
+POLY_MAX_POINTS = 65535   # MI355ZK_POLY_MAX_POINTS: points per call of fr_poly_eval_dev / fr_poly_divide_dev
 R1CS_BATCH_V = 1   # R1CS_BATCH_V of csrc/r1cs.hip: the vectors one workgroup of the batch product carries (its tile; the tests' edge sizes)
 POINTS_PIECE = 1 << 18  # the piece of points_load / points_store (and of the accumulator entry points) when the caller passes 0
 EXP_SAME_SCALAR, FFT_INVERSE, G2_TRUSTED_SUBGROUP = 1, 1, 2   # mode / flag bits of batch_exp, point_fft, sparse_matvec (include/mi355zk.h)
@@ -107,6 +108,10 @@ SIGNATURES = {
     "mi355zk_bn254_fr_h_poly": (_i, [_vp, _vp, _vp, _vp, _sz, _u32, _u32]),
     "mi355zk_bn254_fr_domain_z": (_i, [_u32, _vp, _vp]),
     "mi355zk_bn254_fr_powers_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "mi355zk_bn254_fr_poly_eval_dev": (_i, [_vp, _vp, _sz, _vp, _sz, _vp]),
+    "mi355zk_bn254_fr_poly_divide_dev": (_i, [_vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "mi355zk_selftest_fr_poly_divide": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "mi355zk_fr_poly_geometry": (_i, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
     "mi355zk_ubench_fp_mul": (_i, [_i, _u32, _u32, _vp, _vp, _vp, C.POINTER(C.c_float)]),
     "mi355zk_selftest_g1_record_sum": (_i, [_i, _vp, _vp, _vp, _sz, _sz, _vp]),
     "mi355zk_selftest_g2_record_sum": (_i, [_i, _vp, _vp, _vp, _sz, _sz, _vp]),
