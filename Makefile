@@ -6,8 +6,8 @@ ARCH ?= gfx950
 PKG := phase2-bn254_amd
 SRC := $(PKG)/csrc
 HIPFLAGS ?= --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -Wno-unused-result
-OBJS := build/ntt.o build/msm_g1.o build/msm_g2.o build/msm_partition.o build/api.o build/host_entry.o build/host_ops.o build/bases_cache.o build/host_pools.o build/accumulator_stream.o build/scalar_mul.o build/fixed_base.o build/pairing.o build/fr_random.o build/field_ops.o build/fr_poly.o build/r1cs.o build/point_fft.o build/point_fft_g2.o build/point_diff.o build/codec.o build/records.o build/selftest_dev.o build/selftest_dev_chain.o
-HDRS := $(SRC)/field.hpp $(SRC)/mont_mul_gfx950.inc $(SRC)/curve.hpp $(SRC)/fieldu.hpp $(SRC)/curveu.hpp $(SRC)/device_util.hpp $(SRC)/msm_impl.hpp $(SRC)/msm_digits.hpp $(SRC)/msm_partition.hpp $(SRC)/msm_common.hpp $(SRC)/msm_plan.hpp $(SRC)/msm_join.hpp $(SRC)/msm_pools.hpp $(SRC)/msm_host.hpp $(SRC)/ntt_plan.hpp $(SRC)/ntt_butterfly.hpp $(SRC)/ntt_tables.hpp $(SRC)/host_util.hpp $(SRC)/host_plan.hpp $(SRC)/bases_cache.hpp $(SRC)/host_pools.hpp $(SRC)/device_mem.hpp $(SRC)/pool_pick.hpp $(SRC)/api_internal.hpp $(SRC)/glv.hpp $(SRC)/window_mul.hpp $(SRC)/fixed_base.hpp $(SRC)/pairing.hpp $(SRC)/pairing_constants.inc $(SRC)/chacha.hpp $(SRC)/point_fft_impl.hpp $(SRC)/selftest_dev_ops.hpp $(SRC)/fr_poly.hpp include/mi355zk.h
+OBJS := build/ntt.o build/msm_g1.o build/msm_g2.o build/msm_partition.o build/api.o build/host_entry.o build/host_ops.o build/bases_cache.o build/host_pools.o build/accumulator_stream.o build/scalar_mul.o build/fixed_base.o build/pairing.o build/fr_random.o build/field_ops.o build/fr_poly.o build/fr_inverse.o build/fr_evals.o build/r1cs.o build/point_fft.o build/point_fft_g2.o build/point_diff.o build/codec.o build/records.o build/selftest_dev.o build/selftest_dev_chain.o
+HDRS := $(SRC)/field.hpp $(SRC)/mont_mul_gfx950.inc $(SRC)/curve.hpp $(SRC)/fieldu.hpp $(SRC)/curveu.hpp $(SRC)/device_util.hpp $(SRC)/msm_impl.hpp $(SRC)/msm_digits.hpp $(SRC)/msm_partition.hpp $(SRC)/msm_common.hpp $(SRC)/msm_plan.hpp $(SRC)/msm_join.hpp $(SRC)/msm_pools.hpp $(SRC)/msm_host.hpp $(SRC)/ntt_plan.hpp $(SRC)/ntt_butterfly.hpp $(SRC)/ntt_tables.hpp $(SRC)/host_util.hpp $(SRC)/host_plan.hpp $(SRC)/bases_cache.hpp $(SRC)/host_pools.hpp $(SRC)/device_mem.hpp $(SRC)/pool_pick.hpp $(SRC)/api_internal.hpp $(SRC)/glv.hpp $(SRC)/window_mul.hpp $(SRC)/fixed_base.hpp $(SRC)/pairing.hpp $(SRC)/pairing_constants.inc $(SRC)/chacha.hpp $(SRC)/point_fft_impl.hpp $(SRC)/selftest_dev_ops.hpp $(SRC)/fr_poly.hpp $(SRC)/fr_inverse.hpp include/mi355zk.h
 
 all: $(PKG)/libmi355zk.so oracle tools/bin/ubench_valu tools/bin/ubench_gather tools/bin/ubench_fieldmul tools/bin/ubench_wave_bucket tools/bin/ubench_gather_footprint
 
@@ -31,6 +31,18 @@ clean:
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean
+
+# the batch inversion's variant (b) -- one launch, one inversion per tile -- as a second build of that unit beside the shipped objects:
+# `make inv_one_launch` -> tools/bin/libmi355zk_inv_one_launch.so, what tools/bench_kzg_evals.py loads (MI355ZK_SO) for its same-box A/B
+INV1_OBJS := $(patsubst build/fr_inverse.o,build/fr_inverse_one_launch.o,$(OBJS))
+inv_one_launch: tools/bin/libmi355zk_inv_one_launch.so
+build/fr_inverse_one_launch.o: $(SRC)/fr_inverse.hip $(HDRS)
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -DMI355ZK_INV_ONE_LAUNCH=1 -c $< -o $@
+tools/bin/libmi355zk_inv_one_launch.so: $(INV1_OBJS)
+	@mkdir -p tools/bin
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(INV1_OBJS)
+.PHONY: inv_one_launch
 
 # ---- sanitizer build: the same sources with the HOST side instrumented by AddressSanitizer + UndefinedBehaviorSanitizer
 # (-fno-gpu-sanitize: the gfx950 code objects are the product's).  `make asan` -> tools/bin/libmi355zk_asan.so; run a python process over it with

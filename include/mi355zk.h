@@ -448,6 +448,30 @@ int mi355zk_selftest_fr_poly_divide(uint64_t *q, uint64_t rem[4], const uint64_t
 /* The compile-time geometry: coefficients per lane, coefficients per workgroup (tile), tiles per chunk of the carry kernel -- the sizes at
  * which the code takes another path, for tests. */
 int mi355zk_fr_poly_geometry(uint32_t *run, uint32_t *tile, uint32_t *carry_width);
+/* ---- batch inversion (csrc/fr_inverse.hip): Montgomery's trick over runs, tiles and a product tree per tile; three launches and ONE Fermat
+ * inversion per call.
+ * out[i] = in[i]^-1 (Montgomery Fr in and out, canonical < r, unchecked as for mul_assign); in[i] == 0 gives out[i] = 0.
+ * d_out may be d_in exactly (in place); any other overlap is refused.  d_n_zero: NULL, or a DEVICE uint32 that receives the number of zero
+ * elements.  Asynchronous on `stream`, no host synchronisation; scratch is the library's, per (device, stream).
+ * n == 0 succeeds and launches nothing (and still clears *d_n_zero).  3 = NULL array with n > 0, n >= 2^32, partial overlap. */
+int mi355zk_bn254_fr_batch_inverse_dev(void *d_out, const void *d_in, size_t n, uint32_t *d_n_zero, void *stream);
+/* The same lane routines compiled for the host, in the kernels' grouping into runs, tiles and carry chunks: no device.  out may be in;
+ * n_zero may be NULL.  3 = a NULL array with n > 0, n >= 2^32. */
+int mi355zk_selftest_fr_batch_inverse(uint64_t *out, const uint64_t *in, size_t n, uint32_t *n_zero);
+/* The compile-time geometry: elements per lane, elements per workgroup (tile), tile products per chunk of the second launch. */
+int mi355zk_fr_inverse_geometry(uint32_t *run, uint32_t *tile, uint32_t *carry_width);
+/* ---- a polynomial in EVALUATION form against points (csrc/fr_evals.hip): the evaluation-form twin of fr_poly_divide_dev.
+ * evals: 2^log_n Montgomery Fr on the device, evals[i] = p(omega^i) in natural order, omega = mi355zk_bn254_fr_domain_constants(log_n).
+ * z: n_points x 4 u64 on the HOST (Montgomery), read before the call returns.  For every point j:
+ *   values[j] = p(z_j)                                        at d_values + j * 32 B   (device; may not be NULL)
+ *   q_j[i]    = ((p(x) - p(z_j)) / (x - z_j)) (omega^i)       2^log_n elements at d_q + j * q_stride * 32 B; d_q == NULL: values only
+ * (q_stride in elements; what lies between two quotients is neither read nor written).  z_j may lie IN the domain (z_j = omega^k): then
+ * values[j] = evals[k], and q_j[k] = -omega^-k * sum_{i != k} q_j[i] omega^i.  One batch inversion of the n_points 2^log_n denominators
+ * omega^i - z_j, which are formed where the quotients go (in the library's scratch when d_q is NULL); the table of omega^i is scratch too.
+ * Operand range as for mul_assign.  Asynchronous on `stream`.  3 = NULL evals / values / z, log_n > 28, n_points == 0 or >
+ * MI355ZK_POLY_MAX_POINTS, and with a d_q: q_stride < 2^log_n, a quotient range that overlaps evals or values. */
+int mi355zk_bn254_fr_evals_divide_dev(void *d_q, size_t q_stride, void *d_values, const void *d_evals, uint32_t log_n, const uint64_t *z,
+                                      size_t n_points, void *stream);
 /* Measured Montgomery-product rate of this library (the integer-ALU roofline the kernels are priced
  * against): `blocks` x 256 lanes each run 4 independent chains of `iters` products.  which: 0 Fq, 1 Fr.
  * out[0..3] = a*b^iters (Montgomery arithmetic, lane 0, chain 0) for a parity check; *ms = kernel time. */

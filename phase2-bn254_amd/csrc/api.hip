@@ -319,6 +319,8 @@ void mi355zk_shutdown(void) {
     ntt_release_all();
     scalar_mul_release_all();
     fr_poly_release_all();
+    fr_inverse_release_all();
+    fr_evals_release_all();
     host_entry_release_all();
     msm_release_g1();
     msm_release_g2();

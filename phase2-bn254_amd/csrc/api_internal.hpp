@@ -117,6 +117,9 @@ int fr_into_repr(Fr* d_out, const Fr* d_in, size_t n, hipStream_t st);          
 int fr_powers(Fr* d_out, const Fr& base, const Fr& coeff, size_t n, hipStream_t st);               // out[i] = coeff * base^i (Montgomery)
 // fr_poly.hip
 void fr_poly_release_all();   // the per-(device, stream) scratch of the polynomial division / evaluation (mi355zk_shutdown)
+// fr_inverse.hip, fr_evals.hip
+void fr_inverse_release_all();   // the tile products of the batch inversion, per (device, stream)
+void fr_evals_release_all();     // the omega table, the partial sums and the denominators of evals_divide, per (device, stream)
 
 // fr_random.hip: scalars first .. first + n - 1 of the stream (key, stream_id) of chacha.hpp as canonical FrRepr at d_out (16-byte aligned), enqueued on `st`
 struct FrRandomStream {

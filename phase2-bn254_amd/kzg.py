@@ -13,6 +13,16 @@ polynomial goes from an ifft to a commitment without leaving the device.  Points
 raw affine records ((8,) / (16,) u64, host numpy for single results); the all-zero record is infinity, which is a valid commitment (the
 zero polynomial) and a valid proof (a constant polynomial).  Built from the existing multiexp, sparse product and pairing: no group code
 of its own.
+
+The EVALUATION form (no counterpart in the reference; csrc/fr_inverse.hip, csrc/fr_evals.hip): a polynomial of degree < n = 2^log_n given by
+evals[i] = p(omega^i), omega = the domain's generator, in natural order -- what EvaluationDomain.fft leaves and fr_sparse_matvec_dev writes --
+commits over the Lagrange basis L_i(tau) G (srs_lagrange: one point ifft of the powers) and opens with one batch inversion of the
+denominators omega^i - z instead of an ifft per polynomial:
+  batch_inverse                    1 / a[i], zero for zero
+  commit_evals, commit_evals_many  the same multiexps over lsrs["g1_lagrange"]
+  evaluate_evals, divide_evals     p(z) (barycentric) and the quotient's evaluations, B points per call, z inside the domain included
+  open_evals, open_evals_many      divide_evals + ONE batched multiexp over the Lagrange basis
+The commitments and proofs are the group elements of commit / open, so check and check_many verify them as they are.
 """
 from __future__ import annotations
 
@@ -116,6 +126,60 @@ def divide(coeffs, zs):
     return q, _ints(rem.cpu().numpy())
 
 
+# ---- the evaluation form, Fr half: csrc/fr_inverse.hip, csrc/fr_evals.hip
+
+def batch_inverse(a, out=None, count_zeros=False):
+    """1 / a[i] for any (..., 4) int64 device tensor of Montgomery Fr, zero where a[i] is zero: mi355zk_bn254_fr_batch_inverse_dev, one field
+    inversion per call.  out: None (a new tensor), `a` itself (in place) or a tensor of a's shape that does not overlap it.  With count_zeros
+    the result is (out, the number of zero elements), which waits for the device."""
+    import torch
+
+    if not (getattr(a, "is_cuda", False) and a.dim() >= 1 and a.shape[-1] == 4 and a.element_size() == 8 and a.is_contiguous()):
+        raise ValueError("batch_inverse: a contiguous (..., 4) int64 device tensor of Montgomery Fr")
+    if out is None:
+        out = torch.empty_like(a)
+    elif not (getattr(out, "is_cuda", False) and out.shape == a.shape and out.dtype == a.dtype and out.device == a.device and out.is_contiguous()):
+        raise ValueError("batch_inverse: out has a's shape, dtype and device")
+    n = a.numel() // 4
+    with torch.cuda.device(a.device):
+        zeros = torch.empty(1, dtype=torch.int32, device=a.device) if count_zeros else None
+        _check(_lib.load().mi355zk_bn254_fr_batch_inverse_dev(C.c_void_p(out.data_ptr()) if n else None, C.c_void_p(a.data_ptr()) if n else None, n,
+                                                              C.c_void_p(zeros.data_ptr()) if count_zeros else None, _stream_ptr()), "fr_batch_inverse")
+    return (out, int(zeros.item()) & 0xFFFFFFFF) if count_zeros else out
+
+
+def _evals(evals):
+    evals = _coeffs(evals)
+    n = int(evals.shape[0])
+    if n == 0 or n & (n - 1):
+        raise ValueError("evaluations over a domain: a power of two of them")
+    return evals, n.bit_length() - 1
+
+
+def _evals_divide(evals, zs, with_quotients: bool):
+    import torch
+
+    (evals, log_n), z = _evals(evals), _points(zs)
+    n, b = 1 << log_n, int(z.shape[0])
+    q = torch.empty((b, n, 4), dtype=torch.int64, device=evals.device) if with_quotients else None
+    values = torch.empty((b, 4), dtype=torch.int64, device=evals.device)
+    with torch.cuda.device(evals.device):
+        _check(_lib.load().mi355zk_bn254_fr_evals_divide_dev(C.c_void_p(q.data_ptr()) if with_quotients else None, n, C.c_void_p(values.data_ptr()),
+                                                             C.c_void_p(evals.data_ptr()), log_n, z.ctypes.data_as(C.c_void_p), b, _stream_ptr()),
+               "fr_evals_divide")
+    return q, _ints(values.cpu().numpy())
+
+
+def evaluate_evals(evals, zs) -> list:
+    """[p(z) for z in zs] from p's evaluations over the domain (barycentric; a z in the domain reads its evaluation)"""
+    return _evals_divide(evals, zs, False)[1]
+
+
+def divide_evals(evals, zs):
+    """(q: (B, n, 4) device tensor, [p(z_j)]): q[j, i] = ((p(x) - p(z_j)) / (x - z_j))(omega^i) -- mi355zk_bn254_fr_evals_divide_dev"""
+    return _evals_divide(evals, zs, True)
+
+
 # ---- commitments
 
 def _srs_bases(srs, n: int):
@@ -165,6 +229,54 @@ def open_many(srs, coeffs, zs):
 def open(srs, coeffs, z):  # noqa: A001
     """(p(z), the (8,) proof record)"""
     values, proofs = open_many(srs, coeffs, [z])
+    return values[0], proofs[0]
+
+
+# ---- the evaluation form, group half
+
+def srs_lagrange(srs, log_n: int) -> dict:
+    """srs with "g1_lagrange" = L_i(tau) G for the domain of 2^log_n points (one point ifft of a copy of the first 2^log_n powers) and "log_n"."""
+    n = 1 << int(log_n)
+    g1 = srs["g1"]
+    if n > int(g1.shape[0]):
+        raise ValueError(f"a domain of {n} points over an SRS of {int(g1.shape[0])} powers")
+    import torch
+
+    with torch.cuda.device(g1.device):
+        lagrange = ceremony.point_ifft(g1[:n].clone().contiguous())
+    return {**srs, "g1_lagrange": lagrange, "log_n": int(log_n)}
+
+
+def _lagrange_srs(lsrs, n: int) -> dict:
+    if "g1_lagrange" not in lsrs or n != 1 << lsrs["log_n"]:
+        raise ValueError(f"{n} evaluations need the Lagrange SRS of that domain (srs_lagrange)")
+    return {"g1": lsrs["g1_lagrange"]}
+
+
+def commit_evals(lsrs, evals) -> np.ndarray:
+    """sum_i evals[i] L_i(tau) G: the (8,) record of commit(srs, ifft(evals))"""
+    evals, _ = _evals(evals)
+    return commit(_lagrange_srs(lsrs, int(evals.shape[0])), evals)
+
+
+def commit_evals_many(lsrs, evals_b) -> np.ndarray:
+    """commit_evals for the B polynomials of a (B, n, 4) tensor: one batched multiexp"""
+    if not (getattr(evals_b, "is_cuda", False) and evals_b.dim() == 3 and evals_b.shape[2] == 4):
+        raise ValueError("evals is a (B, n, 4) int64 device tensor")
+    return commit_many(_lagrange_srs(lsrs, int(evals_b.shape[1])), evals_b)
+
+
+def open_evals_many(lsrs, evals, zs):
+    """(values, proofs) of p at every z, from p's evaluations: one evals_divide with B points, one batched multiexp over the Lagrange basis"""
+    evals, _ = _evals(evals)
+    bases = _lagrange_srs(lsrs, int(evals.shape[0]))
+    q, values = divide_evals(evals, zs)
+    return values, commit_many(bases, q)
+
+
+def open_evals(lsrs, evals, z):
+    """(p(z), the (8,) proof record): what open gives for ifft(evals)"""
+    values, proofs = open_evals_many(lsrs, evals, [z])
     return values[0], proofs[0]
 
 

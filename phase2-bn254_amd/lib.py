@@ -112,6 +112,10 @@ SIGNATURES = {
     "mi355zk_bn254_fr_poly_divide_dev": (_i, [_vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp]),
     "mi355zk_selftest_fr_poly_divide": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "mi355zk_fr_poly_geometry": (_i, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
+    "mi355zk_bn254_fr_batch_inverse_dev": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "mi355zk_selftest_fr_batch_inverse": (_i, [_vp, _vp, _sz, C.POINTER(_u32)]),
+    "mi355zk_fr_inverse_geometry": (_i, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
+    "mi355zk_bn254_fr_evals_divide_dev": (_i, [_vp, _sz, _vp, _vp, _u32, _vp, _sz, _vp]),
     "mi355zk_ubench_fp_mul": (_i, [_i, _u32, _u32, _vp, _vp, _vp, C.POINTER(C.c_float)]),
     "mi355zk_selftest_g1_record_sum": (_i, [_i, _vp, _vp, _vp, _sz, _sz, _vp]),
     "mi355zk_selftest_g2_record_sum": (_i, [_i, _vp, _vp, _vp, _sz, _sz, _vp]),
