@@ -6,8 +6,8 @@ ARCH ?= gfx950
 PKG := phase2-bn254_amd
 SRC := $(PKG)/csrc
 HIPFLAGS ?= --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -Wno-unused-result
-OBJS := build/ntt.o build/msm_g1.o build/msm_g2.o build/msm_partition.o build/api.o build/host_entry.o build/host_ops.o build/bases_cache.o build/host_pools.o build/accumulator_stream.o build/scalar_mul.o build/fixed_base.o build/pairing.o build/fr_random.o build/field_ops.o build/fr_poly.o build/fr_inverse.o build/fr_evals.o build/r1cs.o build/point_fft.o build/point_fft_g2.o build/point_diff.o build/codec.o build/records.o build/selftest_dev.o build/selftest_dev_chain.o
-HDRS := $(SRC)/field.hpp $(SRC)/mont_mul_gfx950.inc $(SRC)/curve.hpp $(SRC)/fieldu.hpp $(SRC)/curveu.hpp $(SRC)/device_util.hpp $(SRC)/msm_impl.hpp $(SRC)/msm_digits.hpp $(SRC)/msm_partition.hpp $(SRC)/msm_common.hpp $(SRC)/msm_plan.hpp $(SRC)/msm_join.hpp $(SRC)/msm_pools.hpp $(SRC)/msm_host.hpp $(SRC)/ntt_plan.hpp $(SRC)/ntt_butterfly.hpp $(SRC)/ntt_tables.hpp $(SRC)/host_util.hpp $(SRC)/host_plan.hpp $(SRC)/bases_cache.hpp $(SRC)/host_pools.hpp $(SRC)/device_mem.hpp $(SRC)/pool_pick.hpp $(SRC)/api_internal.hpp $(SRC)/glv.hpp $(SRC)/window_mul.hpp $(SRC)/fixed_base.hpp $(SRC)/pairing.hpp $(SRC)/pairing_constants.inc $(SRC)/chacha.hpp $(SRC)/point_fft_impl.hpp $(SRC)/selftest_dev_ops.hpp $(SRC)/fr_poly.hpp $(SRC)/fr_inverse.hpp include/mi355zk.h
+OBJS := build/ntt.o build/msm_g1.o build/msm_g2.o build/msm_partition.o build/api.o build/host_entry.o build/host_ops.o build/bases_cache.o build/host_pools.o build/accumulator_stream.o build/scalar_mul.o build/fixed_base.o build/pairing.o build/fr_random.o build/field_ops.o build/fr_poly.o build/fr_inverse.o build/fr_scan.o build/fr_evals.o build/r1cs.o build/point_fft.o build/point_fft_g2.o build/point_diff.o build/codec.o build/records.o build/selftest_dev.o build/selftest_dev_chain.o
+HDRS := $(SRC)/field.hpp $(SRC)/mont_mul_gfx950.inc $(SRC)/curve.hpp $(SRC)/fieldu.hpp $(SRC)/curveu.hpp $(SRC)/device_util.hpp $(SRC)/msm_impl.hpp $(SRC)/msm_digits.hpp $(SRC)/msm_partition.hpp $(SRC)/msm_common.hpp $(SRC)/msm_plan.hpp $(SRC)/msm_join.hpp $(SRC)/msm_pools.hpp $(SRC)/msm_host.hpp $(SRC)/ntt_plan.hpp $(SRC)/ntt_butterfly.hpp $(SRC)/ntt_tables.hpp $(SRC)/host_util.hpp $(SRC)/host_plan.hpp $(SRC)/bases_cache.hpp $(SRC)/host_pools.hpp $(SRC)/device_mem.hpp $(SRC)/pool_pick.hpp $(SRC)/api_internal.hpp $(SRC)/glv.hpp $(SRC)/window_mul.hpp $(SRC)/fixed_base.hpp $(SRC)/pairing.hpp $(SRC)/pairing_constants.inc $(SRC)/chacha.hpp $(SRC)/point_fft_impl.hpp $(SRC)/selftest_dev_ops.hpp $(SRC)/fr_poly.hpp $(SRC)/fr_inverse.hpp $(SRC)/fr_scan.hpp include/mi355zk.h
 
 all: $(PKG)/libmi355zk.so oracle tools/bin/ubench_valu tools/bin/ubench_gather tools/bin/ubench_fieldmul tools/bin/ubench_wave_bucket tools/bin/ubench_gather_footprint
 
@@ -43,6 +43,23 @@ tools/bin/libmi355zk_inv_one_launch.so: $(INV1_OBJS)
 	@mkdir -p tools/bin
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(INV1_OBJS)
 .PHONY: inv_one_launch
+
+# the prefix scans with 8 elements per lane instead of 16, as a second build of that unit beside the shipped objects: `make scan_run8` ->
+# tools/bin/libmi355zk_scan_run8.so, what tools/bench_fr_scan.py loads (MI355ZK_SO) for its same-box A/B; `make scan_resources` -> the
+# compiler's register and occupancy remarks for both run lengths, tools/bin/fr_scan_run{8,16}.resources.txt (that tool's VGPR table)
+SCAN8_OBJS := $(patsubst build/fr_scan.o,build/fr_scan_run8.o,$(OBJS))
+scan_run8: tools/bin/libmi355zk_scan_run8.so
+build/fr_scan_run8.o: $(SRC)/fr_scan.hip $(HDRS)
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -DMI355ZK_SCAN_LOG_RUN=3 -c $< -o $@
+tools/bin/libmi355zk_scan_run8.so: $(SCAN8_OBJS)
+	@mkdir -p tools/bin
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(SCAN8_OBJS)
+scan_resources: $(SRC)/fr_scan.hip $(HDRS)
+	@mkdir -p tools/bin build
+	$(HIPCC) $(HIPFLAGS) -DMI355ZK_SCAN_LOG_RUN=3 -Rpass-analysis=kernel-resource-usage -c $< -o build/fr_scan_resources.o 2> tools/bin/fr_scan_run8.resources.txt
+	$(HIPCC) $(HIPFLAGS) -DMI355ZK_SCAN_LOG_RUN=4 -Rpass-analysis=kernel-resource-usage -c $< -o build/fr_scan_resources.o 2> tools/bin/fr_scan_run16.resources.txt
+.PHONY: scan_run8 scan_resources
 
 # ---- sanitizer build: the same sources with the HOST side instrumented by AddressSanitizer + UndefinedBehaviorSanitizer
 # (-fno-gpu-sanitize: the gfx950 code objects are the product's).  `make asan` -> tools/bin/libmi355zk_asan.so; run a python process over it with

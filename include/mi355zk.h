@@ -460,6 +460,44 @@ int mi355zk_bn254_fr_batch_inverse_dev(void *d_out, const void *d_in, size_t n, 
 int mi355zk_selftest_fr_batch_inverse(uint64_t *out, const uint64_t *in, size_t n, uint32_t *n_zero);
 /* The compile-time geometry: elements per lane, elements per workgroup (tile), tile products per chunk of the second launch. */
 int mi355zk_fr_inverse_geometry(uint32_t *run, uint32_t *tile, uint32_t *carry_width);
+/* ---- prefix scans (csrc/fr_scan.hip): running products c_i = a_i c_{i-1} (GrandProductArgument::new, bellman/src/sonic/unhelped/
+ * grand_product_argument.rs:94-172, serial there) and running sums of device-resident rows, over runs, tiles and carry chunks in three launches
+ * (run and tile aggregates; one workgroup per row scans the tile aggregates; apply).  Rows of one tile take the third launch alone.
+ * `rows` vectors of n Montgomery Fr: row r is the n elements at base + r * stride * 32 B (strides in elements; what lies between two rows is
+ * neither read nor written).  n outputs per row in either mode:
+ *   inclusive (default)         out[i] = in[0] o .. o in[i]
+ *   MI355ZK_SCAN_EXCLUSIVE      out[0] = the identity (Montgomery one / zero), out[i] = in[0] o .. o in[i-1]
+ * d_total: NULL, or rows x 32 B on the device: every row's aggregate over all n elements (the identity for n == 0).
+ * A zero is an ORDINARY element of a product: everything after it in its row is zero, exactly as in the serial chain.  This is NOT the
+ * convention of batch_inverse_dev above, which skips zeros.  Every step returns the canonical residue, so the outputs are the serial chain's
+ * byte for byte.  Operand range as for mul_assign (canonical Montgomery Fr, unchecked; an element >= r makes its row UNDEFINED from there on).
+ * d_out == d_in with equal strides is allowed (in place); any other overlap of the two ranges [base, base + ((rows - 1) stride + n) 32), or
+ * of d_total with either, is refused.  Asynchronous on `stream`, no host synchronisation; scratch is the library's, per (device, stream).
+ * n == 0 or rows == 0 launches nothing except what fills d_total.
+ * 3 (before any device work) = a NULL array with non-zero work; n >= 2^32; rows > 65535; a stride < n with rows > 1; unknown flag bits;
+ * partial overlap. */
+#define MI355ZK_SCAN_SUM        1u   /* running sums; default: running products */
+#define MI355ZK_SCAN_EXCLUSIVE  2u   /* out[0] = identity, out[i] = in[0] o .. o in[i-1]; default inclusive: out[i] = in[0] o .. o in[i] */
+int mi355zk_bn254_fr_scan_dev(void *d_out, size_t out_stride, const void *d_in, size_t in_stride, size_t n, size_t rows,
+                              uint32_t flags, void *d_total, void *stream);
+/* The scan of term[i] = num[i] * den[i]^-1: the grand product Z[i+1] = Z[i] num[i] / den[i] of a permutation argument (exclusive product), the
+ * log-derivative sum S[i+1] = S[i] + num[i] / den[i] (exclusive sum).  d_num == NULL: every num[i] is one.  The denominators are copied into
+ * d_out (not when d_out == d_den exactly, with equal strides, which is allowed), inverted there by ONE batch inversion over all the rows -- one
+ * Fermat inversion per call, however many rows -- and the scan runs in place over d_out with num multiplied in at load, so no array of terms
+ * is formed.  den[i] == 0 gives den[i]^-1 = 0 by batch_inverse_dev's convention and the term 0; such elements are counted in *d_n_zero (a DEVICE
+ * uint32, may be NULL; the call clears it first).  d_out may not overlap d_num, nor d_den except as above.  Otherwise as fr_scan_dev, the
+ * refusals included. */
+int mi355zk_bn254_fr_ratio_scan_dev(void *d_out, size_t out_stride, const void *d_num, size_t num_stride, const void *d_den, size_t den_stride,
+                                    size_t n, size_t rows, uint32_t flags, void *d_total, uint32_t *d_n_zero, void *stream);
+/* a[i] += c * b[i] (mul_add_polynomials, bellman/src/sonic/util.rs:855-873); d_b == NULL: a[i] += c, the reference's all-ones vector without the
+ * vector.  c: Montgomery, on the HOST, read before the call returns.  Operand range as for mul_assign.  Asynchronous on `stream`.
+ * 3 = a NULL d_a with n > 0, a NULL c. */
+int mi355zk_bn254_fr_mul_add_dev(void *d_a, const void *d_b, const uint64_t c[4], size_t n, void *stream);
+/* The scan's lane routines compiled for the host, in the kernels' grouping into runs, tiles and carry chunks: one row, no device.  num may be
+ * NULL, out may be in, total may be NULL.  3 = a NULL array with n > 0, n >= 2^32, unknown flag bits. */
+int mi355zk_selftest_fr_scan(uint64_t *out, const uint64_t *in, const uint64_t *num, size_t n, uint32_t flags, uint64_t total[4]);
+/* The compile-time geometry: elements per lane, elements per workgroup (tile), tile aggregates per chunk of the carry launch. */
+int mi355zk_fr_scan_geometry(uint32_t *run, uint32_t *tile, uint32_t *carry_width);
 /* ---- a polynomial in EVALUATION form against points (csrc/fr_evals.hip): the evaluation-form twin of fr_poly_divide_dev.
  * evals: 2^log_n Montgomery Fr on the device, evals[i] = p(omega^i) in natural order, omega = mi355zk_bn254_fr_domain_constants(log_n).
  * z: n_points x 4 u64 on the HOST (Montgomery), read before the call returns.  For every point j:

@@ -122,6 +122,10 @@ extern "C" {
     pub fn mi355zk_fr_poly_geometry(run: *mut u32, tile: *mut u32, carry_width: *mut u32) -> c_int;
     pub fn mi355zk_bn254_fr_batch_inverse_dev(d_out: *mut c_void, d_in: *const c_void, n: usize, d_n_zero: *mut u32, stream: *mut c_void) -> c_int;
     pub fn mi355zk_fr_inverse_geometry(run: *mut u32, tile: *mut u32, carry_width: *mut u32) -> c_int;
+    pub fn mi355zk_bn254_fr_scan_dev(d_out: *mut c_void, out_stride: usize, d_in: *const c_void, in_stride: usize, n: usize, rows: usize, flags: u32, d_total: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_bn254_fr_ratio_scan_dev(d_out: *mut c_void, out_stride: usize, d_num: *const c_void, num_stride: usize, d_den: *const c_void, den_stride: usize, n: usize, rows: usize, flags: u32, d_total: *mut c_void, d_n_zero: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_bn254_fr_mul_add_dev(d_a: *mut c_void, d_b: *const c_void, c: *const u64 /* [4] */, n: usize, stream: *mut c_void) -> c_int;
+    pub fn mi355zk_fr_scan_geometry(run: *mut u32, tile: *mut u32, carry_width: *mut u32) -> c_int;
     pub fn mi355zk_bn254_fr_evals_divide_dev(d_q: *mut c_void, q_stride: usize, d_values: *mut c_void, d_evals: *const c_void, log_n: u32, z: *const u64, n_points: usize, stream: *mut c_void) -> c_int;
     pub fn mi355zk_bn254_g1_sparse_matvec_dev(d_out_affine: *mut c_void, d_bases_affine: *const c_void, n_bases: usize, d_row_ptr: *const u32, d_col: *const u32, d_coeffs: *const c_void, n_rows: usize, nnz: usize, stream: *mut c_void, flags: c_int) -> c_int;
     pub fn mi355zk_bn254_g2_sparse_matvec_dev(d_out_affine: *mut c_void, d_bases_affine: *const c_void, n_bases: usize, d_row_ptr: *const u32, d_col: *const u32, d_coeffs: *const c_void, n_rows: usize, nnz: usize, stream: *mut c_void, flags: c_int) -> c_int;

@@ -8,6 +8,8 @@ Layout:
   pairing.py      the checking half: pairing products on the device, same_ratio[_batch], prepare_verifying_key, verify_proof[s]
   kzg.py          KZG commitments over an accumulator's tau powers: commit, open, check and their batched forms (csrc/fr_poly.hip: the
                   division by (x - z) and the evaluation on the device)
+  grand_product.py  running products and sums of device-resident Fr rows (csrc/fr_scan.hip): prefix_products, prefix_sums, ratio_products,
+                  ratio_sums, mul_add; grand_product_polynomials (sonic's GrandProductArgument::new) and permutation_product on top
   keys.py         hash_to_g2, the key pairs and public-key records of both ceremonies (host work on single points)
   verify.py       the ceremony steps and their checks: contribute_mpc_parameters, verify_contribution, verify_mpc_parameters,
                   contribute_response, verify_transform, next_challenge -- one pairing launch per verification
@@ -24,7 +26,7 @@ Layout:
 The directory name carries a hyphen (it is the reference's name); import it through the
 repo-root shim module `phase2_bn254_amd`.
 """
-from . import bellman, ceremony, circom, generator, keys, kzg, lib, pairing, prover, shard, stream, verify  # noqa: F401
+from . import bellman, ceremony, circom, generator, grand_product, keys, kzg, lib, pairing, prover, shard, stream, verify  # noqa: F401
 from .bellman import (  # noqa: F401
     DensityTracker,
     EvaluationDomain,

@@ -320,6 +320,7 @@ void mi355zk_shutdown(void) {
     scalar_mul_release_all();
     fr_poly_release_all();
     fr_inverse_release_all();
+    fr_scan_release_all();
     fr_evals_release_all();
     host_entry_release_all();
     msm_release_g1();

@@ -113,10 +113,13 @@ int records_pack_run(int group, const void* d_raw, size_t n, const RecordLayout&
 
 // field_ops.hip
 int fr_h_combine(Fr* d_a, const Fr* d_b, const Fr* d_c, size_t n, const Fr& zinv, hipStream_t st);   // a[i] = (a[i] * b[i] - c[i]) * zinv, one pass
+int fr_mul_add(Fr* d_a, const Fr* d_b, const Fr& c, size_t n, hipStream_t st);                        // a[i] += c * b[i] (d_b NULL: a[i] += c)
 int fr_into_repr(Fr* d_out, const Fr* d_in, size_t n, hipStream_t st);                                // Montgomery -> canonical (d_out may alias d_in)
 int fr_powers(Fr* d_out, const Fr& base, const Fr& coeff, size_t n, hipStream_t st);               // out[i] = coeff * base^i (Montgomery)
 // fr_poly.hip
 void fr_poly_release_all();   // the per-(device, stream) scratch of the polynomial division / evaluation (mi355zk_shutdown)
+// fr_scan.hip
+void fr_scan_release_all();   // the tile aggregates of the prefix scans, per (device, stream)
 // fr_inverse.hip, fr_evals.hip
 void fr_inverse_release_all();   // the tile products of the batch inversion, per (device, stream)
 void fr_evals_release_all();     // the omega table, the partial sums and the denominators of evals_divide, per (device, stream)

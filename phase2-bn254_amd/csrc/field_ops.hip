@@ -38,6 +38,12 @@ __global__ void __launch_bounds__(256) fr_pointwise_kernel(Fr* __restrict__ a, c
   }
 }
 
+// a[i] += c b[i] (b == nullptr: a[i] += c): mul_add_polynomials, bellman/src/sonic/util.rs:855-873, the all-ones vector without the vector
+__global__ void __launch_bounds__(256) fr_mul_add_kernel(Fr* __restrict__ a, const Fr* __restrict__ b, uint64_t n, Fr c) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+    st(a + i, add(ld(a + i), b != nullptr ? mul(c, ld(b + i)) : c));
+}
+
 // a[i] = (a[i] * b[i] - c[i]) * zinv: mul_assign, sub_assign and divide_by_z_on_coset of the prover's H polynomial (prover.rs:232-236) in one
 // pass -- three 32-byte loads and one store per element (128 B) where the three passes move 256 B.  Every step returns the canonical
 // residue, as the separate kernels do, so the result is theirs byte for byte.
@@ -136,6 +142,14 @@ int fr_h_combine(Fr* d_a, const Fr* d_b, const Fr* d_c, size_t n, const Fr& zinv
   uint64_t blocks = (n + 255) / 256;
   if (blocks > 16384) blocks = 16384;
   hipLaunchKernelGGL(fr_h_combine_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_a, d_b, d_c, (uint64_t)n, zinv);
+  ZK_HIP(hipGetLastError());
+  return ZK_OK;
+}
+int fr_mul_add(Fr* d_a, const Fr* d_b, const Fr& c, size_t n, hipStream_t st) {
+  if (n == 0) return ZK_OK;
+  uint64_t blocks = (n + 255) / 256;
+  if (blocks > 16384) blocks = 16384;
+  hipLaunchKernelGGL(fr_mul_add_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_a, d_b, (uint64_t)n, c);
   ZK_HIP(hipGetLastError());
   return ZK_OK;
 }
@@ -534,6 +548,14 @@ int mi355zk_selftest_g2_scalar_mul_u(const uint64_t affine_pt[16], const uint64_
 
 int mi355zk_bn254_fr_mul_assign_dev(void* d_a, const void* d_b, size_t n, void* stream) { return zk::abi_guard([&]() -> int { return zk::pointwise(d_a, d_b, n, stream, 0); }); }
 int mi355zk_bn254_fr_sub_assign_dev(void* d_a, const void* d_b, size_t n, void* stream) { return zk::abi_guard([&]() -> int { return zk::pointwise(d_a, d_b, n, stream, 1); }); }
+int mi355zk_bn254_fr_mul_add_dev(void* d_a, const void* d_b, const uint64_t c[4], size_t n, void* stream) {
+  return zk::abi_guard([&]() -> int {
+    if (!c || (n && !d_a)) return ZK_ERR_BAD_ARGS;
+    zk::Fr cc;
+    std::memcpy(&cc, c, 32);
+    return zk::fr_mul_add((zk::Fr*)d_a, (const zk::Fr*)d_b, cc, n, (hipStream_t)stream);
+  });
+}
 int mi355zk_bn254_fr_into_repr_dev(void* d_out, const void* d_in, size_t n, void* stream) {
   return zk::abi_guard([&]() -> int {
     if ((!d_out || !d_in) && n) return ZK_ERR_BAD_ARGS;

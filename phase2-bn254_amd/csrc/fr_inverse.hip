@@ -170,10 +170,10 @@ int inverse_run(Fr* d_out, const Fr* d_in, size_t n, size_t stride, size_t rows,
 
 }  // namespace
 
-int fr_inverse_rows(Fr* d_io, size_t n, size_t stride, size_t rows, hipStream_t st) {
+int fr_inverse_rows(Fr* d_io, size_t n, size_t stride, size_t rows, hipStream_t st, uint32_t* d_n_zero) {
   if (n == 0 || rows == 0) return ZK_OK;
   if ((uint64_t)n >= (1ull << 32) || rows > 65535 || stride < n) return ZK_ERR_BAD_ARGS;
-  return inverse_run(d_io, d_io, n, stride, rows, nullptr, st);
+  return inverse_run(d_io, d_io, n, stride, rows, d_n_zero, st);
 }
 
 void fr_inverse_release_all() {

@@ -161,7 +161,8 @@ inline uint32_t inv_batch_host(Fr* out, const Fr* in, size_t n) {
 #if defined(__HIPCC__)
 // fr_inverse.hip, for the other units of the library: `rows` vectors of n elements, row r at d_io + r * stride, inverted IN PLACE with one
 // Fermat inversion for all of them (what lies between two rows is neither read nor written).  n < 2^32, rows <= 65535.  Enqueued on `st`.
-int fr_inverse_rows(Fr* d_io, size_t n, size_t stride, size_t rows, hipStream_t st);
+// d_n_zero: NULL, or a device counter (cleared by the caller) that the zeros of all the rows are added to.
+int fr_inverse_rows(Fr* d_io, size_t n, size_t stride, size_t rows, hipStream_t st, uint32_t* d_n_zero = nullptr);
 #endif
 
 }  // namespace zk

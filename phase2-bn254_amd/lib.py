@@ -24,7 +24,8 @@ FIXED_BASES_LANE_TARGET = 262144  # MI355ZK_FIXED_BASES_LANE_TARGET: the lane co
 SHIFTED_DIFFERENCE_K = 16   # MI355ZK_SHIFTED_DIFFERENCE_K: outputs per shared inversion of g1_shifted_difference
 R1CS_MAX_VECTORS = 65535   # MI355ZK_R1CS_MAX_VECTORS: vectors per call of fr_sparse_matvec_batch_dev / fr_r1cs_check_dev
 POLY_MAX_POINTS = 65535   # MI355ZK_POLY_MAX_POINTS: points per call of fr_poly_eval_dev / fr_poly_divide_dev
-R1CS_BATCH_V = 1   # R1CS_BATCH_V of csrc/r1cs.hip: the vectors one workgroup of the batch product carries (its tile; the tests' edge sizes)
+SCAN_SUM, SCAN_EXCLUSIVE, SCAN_MAX_ROWS = 1, 2, 65535   # MI355ZK_SCAN_*: flags of fr_scan_dev / fr_ratio_scan_dev, and their rows per call
+R1CS_BATCH_V = 1  # R1CS_BATCH_V of csrc/r1cs.hip: the vectors one workgroup of the batch product carries (its tile; the tests' edge sizes)
 POINTS_PIECE = 1 << 18  # the piece of points_load / points_store (and of the accumulator entry points) when the caller passes 0
 EXP_SAME_SCALAR, FFT_INVERSE, G2_TRUSTED_SUBGROUP = 1, 1, 2   # mode / flag bits of batch_exp, point_fft, sparse_matvec (include/mi355zk.h)
 
@@ -115,6 +116,11 @@ SIGNATURES = {
     "mi355zk_bn254_fr_batch_inverse_dev": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "mi355zk_selftest_fr_batch_inverse": (_i, [_vp, _vp, _sz, C.POINTER(_u32)]),
     "mi355zk_fr_inverse_geometry": (_i, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
+    "mi355zk_bn254_fr_scan_dev": (_i, [_vp, _sz, _vp, _sz, _sz, _sz, _u32, _vp, _vp]),
+    "mi355zk_bn254_fr_ratio_scan_dev": (_i, [_vp, _sz, _vp, _sz, _vp, _sz, _sz, _sz, _u32, _vp, _vp, _vp]),
+    "mi355zk_bn254_fr_mul_add_dev": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "mi355zk_selftest_fr_scan": (_i, [_vp, _vp, _vp, _sz, _u32, _vp]),
+    "mi355zk_fr_scan_geometry": (_i, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
     "mi355zk_bn254_fr_evals_divide_dev": (_i, [_vp, _sz, _vp, _vp, _u32, _vp, _sz, _vp]),
     "mi355zk_ubench_fp_mul": (_i, [_i, _u32, _u32, _vp, _vp, _vp, C.POINTER(C.c_float)]),
     "mi355zk_selftest_g1_record_sum": (_i, [_i, _vp, _vp, _vp, _sz, _sz, _vp]),
